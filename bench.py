@@ -10,8 +10,12 @@ synthetic (the lego rig's spiral poses; no dataset on the box) and resident in H
 Multi-GPU (torchrun, one process per GPU): each rank trains its own 4096-ray shard (weak
 scaling); gradients are all-reduced once per step over RCCL (one 67 MB bucket).
 
-Prints ONE JSON line (rank 0) with `roofline` for the dominant kernel (HIP-event timed inside the
-timed region) and `cpu_baseline` (the oracle's CPU training step on a bounded sample, N=1 only).
+Prints ONE JSON line (rank 0). A plain run sets up, warms up, times `--steps` steps and prints the
+headline (`value`, `ms_per_step`). `--full` adds the legs that take runs of their own: `roofline` /
+`ops` / `kernels` (the same launches timed with HIP events), `fresh_rays` (a new batch every step),
+`gpu_clocks`, `psnr_vs_reference` and `cpu_baseline` (the oracle's CPU training step on a bounded
+sample, N=1 only). `--dump-outputs DIR` writes what the run's last step of the timed path returned
+and the MLP state it left as DIR/<name>.npy, reproducibly from run to run (dump_outputs).
 """
 import argparse
 import json
@@ -226,11 +230,21 @@ def parse():
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=40)
     ap.add_argument("--rays", type=int, default=4096)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beyond the headline: per-kernel HIP-event timing "
+                         "and rooflines (--profile-kernels), the fresh-rays leg (--fresh-rays), the GPU clocks, the "
+                         "committed PSNR comparison and the CPU baseline (unless --no-cpu-baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the timed path returns and the MLP state it leaves as "
+                         "DIR/<name>.npy (rank 0), taken from a few further steps of it from the initial state so "
+                         "that runs can be compared (see dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-rays", type=int, default=4096, help="rays of the CPU leg's timed iterations (the bench batch)")
     ap.add_argument("--cpu-warmup", type=int, default=6)
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--profile-kernels", type=int, default=1, help="record HIP events per kernel in the timed region")
+    ap.add_argument("--profile-kernels", type=int, default=1,
+                    help="with --full: record HIP events per kernel (eager: in the timed region; graph: in further "
+                         "eager iterations after it)")
     ap.add_argument("--workload", default="lego", choices=sorted(WORKLOADS),
                     help="BASELINE config: lego (configs[1], the headline), fern (configs[2], LLFF NDC), "
                          "scannet (configs[3], normals + structural priors, meant for --gpus 8), "
@@ -271,12 +285,19 @@ def parse():
     ap.add_argument("--coarse-reuse", type=int, default=1,
                     help="1: the fine pass reuses the coarse pass's hash encoding (DESIGN §8.5); 0: re-encode (A/B)")
     ap.add_argument("--fresh-rays", type=int, default=1,
-                    help="also time the step with a new ray batch every iteration (train()'s no_batching draw: "
+                    help="with --full: also time the step with a new ray batch every iteration (train()'s no_batching draw: "
                          "one random view, N_rand random pixels; blender-rig workloads, graph mode): "
                          "fresh_rays_ms_per_step in the line")
     ap.add_argument("--mode", default="train", choices=["train", "render"],
                     help="train: full training iteration (the metric); render: render-only (eval modules, no grad)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # the legs beyond the headline run only with --full
+    a.profile_kernels = a.profile_kernels if a.full else 0
+    a.fresh_rays = a.fresh_rays if a.full else 0
+    a.no_cpu_baseline = a.no_cpu_baseline or not a.full
+    return a
 
 
 # BASELINE.json configs measured by this bench (the default line is configs[1], lego)
@@ -502,6 +523,70 @@ def fresh_rays_leg(a, kw, opt, args, arena, hook, post, world, dev, it, rank):
     return 1e3 * elapsed / a.steps, it, bool(st.captures > 0)
 
 
+DUMP_MAX_BYTES = 64 * 1000 * 1000
+# --dump-outputs (train): steps of the timed path replayed from the run's initial state; RAdam's update is
+# a no-op until N_sma >= 5 at step 6 (radam.py:63-92), so 8 steps = 5 moment-only steps + 3 real updates
+DUMP_REPLAY_STEPS = 8
+
+
+def snapshot_state(kw, params):
+    """The training state before the first step (parameters, module buffers, the embedder's call
+    count), for restore_state; RAdam has no state yet."""
+    mods = [m for m in (kw.get("network_fn"), kw.get("network_fine"), kw.get("embed_fn")) if m is not None]
+    return {"params": [p.detach().clone() for p in params],
+            "buffers": [(b, b.detach().clone()) for m in mods for b in m.buffers()],
+            "current_step": getattr(kw["embed_fn"], "current_step", None)}
+
+
+def restore_state(snap, kw, params, opt):
+    """Back to snapshot_state's state, in place (a captured step keeps the addresses): parameters and
+    buffers copied back, RAdam's moments zeroed and its step counts at 0."""
+    with torch.no_grad():
+        for p, s in zip(params, snap["params"]):
+            p.copy_(s)
+        for b, s in snap["buffers"]:
+            b.copy_(s)
+        for st in opt.state.values():
+            st["step"] = 0
+            st["exp_avg"].zero_()
+            st["exp_avg_sq"].zero_()
+    if snap["current_step"] is not None:
+        kw["embed_fn"].current_step = snap["current_step"]
+
+
+def dump_outputs(path, mode, loss, psnr, mlp_params, rendered):
+    """--dump-outputs: what a caller of the timed path holds after the run's last step of it, as
+    DIR/<name>.npy in float32, so that two runs or two builds can be compared output for output.
+    train: the step's return values (`loss`, `psnr`), `mlp_params` (every MLP parameter as the step
+    left it, flattened in optimizer order) and `mlp_grads` (their gradients of that step).
+    The state the timed steps leave is not reproducible: the unordered fp32 atomic sums of the
+    backward differ at rounding level from run to run, and RAdam turns that into steps of either sign
+    wherever a gradient is itself rounding noise (the tables' group has eps 1e-15, run_nerf.py's), so
+    two runs of one build drift apart — parameters within 2e-7 after 25 steps, 1e-2 after 100, and
+    altogether after 440. So the dump is taken from DUMP_REPLAY_STEPS further steps of the same timed
+    path (the same captured graph and inputs) that main() runs after the timed ones from the run's
+    initial parameters and optimizer state (restore_state): the same inputs every run, and outputs
+    that repeat within fp32 rounding. The hash tables are left out: after three updates a few rows in
+    a million already differ by ~lr (the sign effect above), too faint in the forward for the loss.
+    render: the last timed step's `rgb`, `depth` and `acc` maps (no state changes between steps)."""
+    out = {}
+    if mode == "train":
+        out["loss"] = loss.detach().reshape(1)
+        out["psnr"] = psnr.detach().reshape(1)
+        out["mlp_params"] = torch.cat([p.detach().reshape(-1) for p in mlp_params])
+        if all(p.grad is not None for p in mlp_params):
+            out["mlp_grads"] = torch.cat([p.grad.detach().reshape(-1) for p in mlp_params])
+    else:
+        out.update(rendered)
+    arrays = {k: (v.float().cpu().numpy() if torch.is_tensor(v) else v).astype(np.float32) for k, v in out.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte bound")
+    os.makedirs(path, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), v)
+
+
 def launch_ranks(a):
     """`--gpus N` (N > 1) without torchrun's environment: start the N rank processes here (torch's
     elastic launcher as a CHILD process, one rank per GPU, rendezvous on 127.0.0.1) and return its
@@ -620,6 +705,7 @@ def main():
         hook = (lambda: arena.allreduce_mean()) if (world > 1 or force_dist) else None
 
     gstep = None
+    rendered = {}                # render mode: the last step's maps (for --dump-outputs)
     if a.mode == "train" and a.graph:
         from indoor_nerf_amd.graphs import GraphedTrainStep
         gstep = GraphedTrainStep(rays, target, kw, opt, args, H=H, W=W, K=K, grad_hook=hook,
@@ -637,9 +723,11 @@ def main():
 
         def step(i):
             with torch.no_grad():
-                rgb, _, _, _ = nerf.render(H, W, K, chunk=args.chunk, rays=rays, **kw_test)
+                rgb, depth, acc, _ = nerf.render(H, W, K, chunk=args.chunk, rays=rays, **kw_test)
+            rendered.update(rgb=rgb, depth=depth, acc=acc)
             return rgb.mean(), rgb.mean()
 
+    snap = snapshot_state(kw, params) if (a.dump_outputs and a.mode == "train") else None
     it = 1
     if wl.get("quantized") and a.mode == "render":
         # calibrate the quantizers with one training iteration first (they calibrate on their
@@ -670,13 +758,31 @@ def main():
     elapsed = time.perf_counter() - t0
     if gstep is not None:
         gstep.check()              # every replay fetched its own scalar slot (outside the timed region)
-    clocks = gpu_clocks() if rank == 0 else None
+    clocks = gpu_clocks() if (rank == 0 and a.full) else None
     recs = _lib.timing_records()
     _lib.set_timing(False)
     if world > 1:
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs:
+        # (a replayed graph returns the same two tensors every step: keep the last timed step's values)
+        loss, psnr = loss.detach().clone(), psnr.detach().clone()
+        out_loss, out_psnr = loss, psnr
+        if snap is not None:
+            # the timed path replayed from the initial state (dump_outputs: the trained state drifts from
+            # run to run); every rank runs it, rank 0 writes
+            restore_state(snap, kw, params, opt)
+            for _ in range(DUMP_REPLAY_STEPS):
+                out_loss, out_psnr = step(it)
+                it += 1
+            if zero:
+                sharded.wait_params()
+            torch.cuda.synchronize()
+            if gstep is not None:
+                gstep.check()
+        if rank == 0:
+            dump_outputs(a.dump_outputs, a.mode, out_loss, out_psnr, grad_vars, rendered)
 
     # per-kernel timing: eager -> HIP-event pairs around every launch of the timed region. graph ->
     # torch on ROCm cannot capture timing events, so K further iterations of the same launches run
@@ -771,6 +877,7 @@ def main():
         "n_gpus": a.gpus,
         "steps": a.steps,
         "warmup": a.warmup,
+        "full": bool(a.full),
         "ms_per_step": round(1e3 * elapsed / a.steps, 3),
         "higher_is_better": True,
         "scaling": a.scaling,
@@ -807,7 +914,7 @@ def main():
                                  f"({'ZeRO-1' if zero else 'all-reduce'}), collectives of one rank")
     # north star "PSNR within 0.1 dB of reference": the committed result of tests/test_gpu_converge.py
     # (the reference trained on F19 six times vs six HIP runs; late-phase mean PSNR difference per metric)
-    for name in [f"r0{k}_psnr_vs_reference.json" for k in range(6, 1, -1)]:
+    for name in [f"r0{k}_psnr_vs_reference.json" for k in range(6, 1, -1)] if a.full else []:
         pv = os.path.join(ROOT, "profiles", name)
         if os.path.exists(pv):
             pj = json.load(open(pv))

@@ -414,7 +414,14 @@ def test_tv_bins_in_hash_bin_launch(nerf, gpu, det):
     front) against their own nerf_tv_bwd_bin launch: same workspace chunks, so one training iteration
     (both nets, coarse-feature reuse, TV) gives bit-identical gradients in deterministic mode, and
     gradients within the owner's summation-order rounding (fp64 LDS sums, one fp32 rounding: 1e-6 of
-    each table's largest) in the default mode."""
+    each table's largest) in the default mode. The MLP gradients do not pass through the bins: in the
+    default mode the two runs differ there only by the arrival order of the weight-gradient flush
+    (csrc/field_x6.hip: every element is the fp32 atomic sum of one partial per block, at most
+    kMlpBwdMaxBlocks = 256 of them). Two orders of a B-term fp32 sum differ by at most
+    2 (B - 1) 2^-24 of the terms' absolute sum (Higham, Accuracy and Stability, §4.2), so they are
+    held to 2 x 255 x 2^-24 = 3.04e-5 of each tensor's largest (the partials' absolute sum taken at
+    the tensor's largest element); 1e-6 of it is ~17 roundings of the largest element, which 256
+    unordered adds exceed from run to run (1.17e-6 seen on the same library that passes elsewhere)."""
     from indoor_nerf_amd import hashgrid, model
     lo, hi = blender_bbox()
     args = nerf.make_args(bounding_box=(torch.from_numpy(lo), torch.from_numpy(hi)), finest_res=1024, N_samples=64,
@@ -463,4 +470,5 @@ def test_tv_bins_in_hash_bin_launch(nerf, gpu, det):
             assert torch.equal(x, y), f"parameter {i}: TV bins in the hash bin launch differ"
         else:   # default mode: the MLP's weight-gradient atomics and the owner's fp64 LDS sums are unordered
             m = float(y.abs().max())
-            assert float((x - y).abs().max()) <= 1e-6 * m, f"parameter {i}"
+            bar = 2 * 255 * 2.0 ** -24 if i < len(grad_vars) else 1e-6
+            assert float((x - y).abs().max()) <= bar * m, f"parameter {i}"

@@ -4,6 +4,7 @@
 set -o pipefail
 out=$1; shift
 mkdir -p gpurun_out/$out
+BENCH_ARGS="--full $BENCH_ARGS"     # the lines' `ops` (tools/ab_summary.py) and fresh-rays leg
 for r in 1 2 3; do
   for v in "$@"; do
     if [ $v = default ]; then L=indoor-nerf_amd/libnerfhip.so; else L=build/variants/$v/libnerfhip.so; fi

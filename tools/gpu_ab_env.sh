@@ -3,6 +3,7 @@
 set -o pipefail
 out=gpurun_out/$1; rounds=$2; wl=$3; shift 3
 mkdir -p $out
+BENCH_ARGS="--full $BENCH_ARGS"     # the lines' `ops` (tools/ab_summary.py) and fresh-rays leg
 for r in $(seq $rounds); do
   for v in "$@"; do
     echo -n "{\"variant\": \"${wl}_$v\", \"round\": $r, \"result\": " >> $out/results.jsonl

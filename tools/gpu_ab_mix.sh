@@ -1,6 +1,7 @@
 # Same box, alternating: bench variants given as DIR:ENV (DIR = a tree with its own built library, "."
 # for this one; ENV = one VAR=VALUE or "-"), JSON lines in gpurun_out/OUT/results.jsonl.
 # usage: tools/gpu_ab_mix.sh OUT ROUNDS WORKLOAD DIR:ENV ...
+# BENCH_ARGS: further bench arguments, e.g. --full (per-op times, fresh-rays leg) where every DIR's bench has it
 set -o pipefail
 out=$PWD/gpurun_out/$1; rounds=$2; wl=$3; shift 3
 mkdir -p $out

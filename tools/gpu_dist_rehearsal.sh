@@ -7,7 +7,7 @@ mkdir -p gpurun_out/dist
 run() {  # name backend args...
   local name=$1 be=$2; shift 2
   NERF_DIST_BACKEND=$be timeout -k 10 240 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 \
-      --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus 2 --steps 8 --warmup 4 \
+      --master-addr 127.0.0.1 --master-port $((29600 + RANDOM % 300)) bench.py --gpus 2 --steps 8 --warmup 4 --full \
       --no-cpu-baseline "$@" > gpurun_out/dist/$name.json 2> gpurun_out/dist/$name.err
 }
 run gloo_weak_zero gloo --zero 1 || exit 1

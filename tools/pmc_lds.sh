@@ -9,7 +9,7 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_ACTIVE_INST_LDS \
     SQ_LDS_BANK_CONFLICT SQ_INSTS_LDS SQ_INSTS_VMEM SQ_ACTIVE_INST_ANY \
-    --output-format csv -d "$OUT" -o sq -- python3 "$ROOT/bench.py" --no-cpu-baseline --profile-kernels 0 \
+    --output-format csv -d "$OUT" -o sq -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --profile-kernels 0 \
     --steps 3 --warmup 2 "$@" > "$OUT/sq.log" 2>&1
 python3 - "$OUT/sq_counter_collection.csv" <<'PY' > "$OUT/sq_summary.txt"
 import collections, csv, sys

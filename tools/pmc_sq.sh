@@ -10,11 +10,11 @@ mkdir -p "$OUT"
 cd /tmp && export TMPDIR=/tmp
 timeout -s KILL 120 rocprofv3 --pmc SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY \
     SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_INST_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS \
-    --output-format csv -d "$OUT" -o a -- python3 "$ROOT/bench.py" --no-cpu-baseline --profile-kernels 0 \
+    --output-format csv -d "$OUT" -o a -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --profile-kernels 0 \
     --steps 3 --warmup 2 "$@" > "$OUT/a.log" 2>&1
 timeout -s KILL 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_MFMA SQ_INSTS_LDS SQ_INSTS_SALU SQ_INSTS_SMEM \
     SQ_INSTS_VMEM SQ_LDS_BANK_CONFLICT SQ_WAVES \
-    --output-format csv -d "$OUT" -o b -- python3 "$ROOT/bench.py" --no-cpu-baseline --profile-kernels 0 \
+    --output-format csv -d "$OUT" -o b -- python3 "$ROOT/bench.py" --full --no-cpu-baseline --profile-kernels 0 \
     --steps 3 --warmup 2 "$@" > "$OUT/b.log" 2>&1
 python3 - "$OUT/a_counter_collection.csv" "$OUT/b_counter_collection.csv" <<'PY' > "$OUT/sq_summary.txt"
 import collections, csv, sys
