@@ -764,6 +764,48 @@ int nerf_priors_bwd(const float* d_depth, const float* d_normals, const float* d
 int nerf_nearest_pixel(const float* d_xy, int64_t n, const int64_t* d_idx1, int64_t n_query, int64_t* d_idx2,
                        float* d_dist, void* stream);
 
+/* ---- occupancy grid: empty-space skipping for forward-only rendering (csrc/occupancy.hip) -------
+ * Additive entries (the ABI version stays 12). The box is cut into res^3 cells (1 <= res <= 1024);
+ * cell (ix, iy, iz) has id (ix*res + iy)*res + iz and owns bit (id & 31) of word id >> 5 of d_bits,
+ * uint32[ceil(res^3 / 32)] (bits past res^3 are 0). Cell rule, per axis, in fp32 with
+ * cell = (bbox_max - bbox_min) / res: index = min((int)floor((clamp(x, min, max) - min) / cell), res - 1),
+ * and a point is a candidate only if x == clamp(x) on all three axes (the hash encoder's keep flag).
+ * The box must satisfy the hash grid's bounds (|bounds| 0 or in [2^-40, 2^40], cells >= 2^-16 of them).
+ *
+ * nerf_occ_cell_points: d_pts [n_cells * n_per_cell, 3] = sample positions of cells [cell_begin,
+ *   cell_begin + n_cells): sample 0 is the cell centre, sample k > 0 uniform in the cell from
+ *   Philox4x32-10 (seed, offset) at counter cell * n_per_cell + k (its first three uniforms: a grid does
+ *   not depend on how the cells are chunked). Every position classifies into its own cell.
+ * nerf_occ_mark: d_raw [n_cells * n_per_cell, 4] = the field's raw rows at those positions; the bit of
+ *   a cell is ORed with any_k(d_raw[.., 3] > sigma_thresh). cell_begin must be a multiple of 64.
+ * nerf_occ_dilate: d_bits_out = d_bits_in with every cell set that has a set cell in its 3x3x3
+ *   neighbourhood (clipped at the faces); the two bitfields must not alias.
+ * nerf_occ_query: d_out[p] (uint8) = point p is inside the box and its cell's bit is set.
+ * nerf_occ_compact: the kept points (query = 1) of a field call over d_pts [n_points, 3], point p on ray
+ *   p / samples_per_ray, whose view encoding comes from d_sh_rays (nerf_sample_stratified_sh's [R, 40]
+ *   records) or d_viewdirs [R, 3] (exactly one non-NULL). `stages` bit 0: count — d_counts[0] = number of
+ *   kept points, and the per-block counts in the workspace (nerf_occ_compact_workspace_bytes(n_points));
+ *   bit 1: scatter — d_rows[i] = the i-th kept point (ascending), d_pts_c [capacity, 3] its position,
+ *   d_sh_c [capacity, 16] the fp32 SH4 coefficients of its ray (the nerf_mlp_* entries' d_sh at
+ *   sh_stride 16), for i < capacity <= n_points, and an all-zero row of d_raw [n_points, 4] for every
+ *   skipped point; it reads the workspace a count stage over the same points and bits left. 3 = both
+ *   in one call (capacity = n_points needs no host read); 1, a host read of the count, then 2 with
+ *   capacity = count sizes the outputs to the kept points. */
+int nerf_occ_cell_points(const float* bbox_min, const float* bbox_max, int res, int64_t cell_begin, int64_t n_cells,
+                         int n_per_cell, unsigned long long seed, unsigned long long offset, float* d_pts,
+                         void* stream);
+int nerf_occ_mark(const float* d_raw, int res, int64_t cell_begin, int64_t n_cells, int n_per_cell,
+                  float sigma_thresh, uint32_t* d_bits, void* stream);
+int nerf_occ_dilate(const uint32_t* d_bits_in, int res, uint32_t* d_bits_out, void* stream);
+int nerf_occ_query(const float* d_pts, int64_t n_points, const float* bbox_min, const float* bbox_max, int res,
+                   const uint32_t* d_bits, uint8_t* d_out, void* stream);
+size_t nerf_occ_compact_workspace_bytes(int64_t n_points);
+int nerf_occ_compact(const float* d_pts, int64_t n_points, const float* d_sh_rays, const float* d_viewdirs,
+                     int64_t samples_per_ray, const float* bbox_min, const float* bbox_max, int res,
+                     const uint32_t* d_bits, int stages, int64_t capacity, int32_t* d_rows, int32_t* d_counts,
+                     float* d_pts_c, float* d_sh_c, float* d_raw, void* d_workspace, size_t workspace_bytes,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,12 @@ SIGNATURES = {
                                     c_i64, c_vp, c_vp],
     "nerf_train_loss_bwd": [c_vp, c_vp, c_vp, c_i64, ctypes.c_float, c_int, ctypes.c_float, c_vp, c_vp, c_vp,
                             c_vp, c_vp, c_vp, c_vp],
+    "nerf_occ_cell_points": [c_f32p, c_f32p, c_int, c_i64, c_i64, c_int, c_u64, c_u64, c_vp, c_vp],
+    "nerf_occ_mark": [c_vp, c_int, c_i64, c_i64, c_int, ctypes.c_float, c_vp, c_vp],
+    "nerf_occ_dilate": [c_vp, c_int, c_vp, c_vp],
+    "nerf_occ_query": [c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp],
+    "nerf_occ_compact": [c_vp, c_i64, c_vp, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_int, c_i64, c_vp, c_vp, c_vp,
+                         c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
 }
 
 _lib = None
@@ -271,6 +277,9 @@ def load():
     lib.nerf_active_rows_workspace_bytes.argtypes = [c_i64]
     lib.nerf_quant_packed_bytes.restype = ctypes.c_size_t
     lib.nerf_quant_packed_bytes.argtypes = [c_int, c_int]
+    if hasattr(lib, "nerf_occ_compact_workspace_bytes"):   # additive (an older A/B variant may lack it)
+        lib.nerf_occ_compact_workspace_bytes.restype = ctypes.c_size_t
+        lib.nerf_occ_compact_workspace_bytes.argtypes = [c_i64]
     if hasattr(lib, "nerf_mlp_h3_bytes"):   # ABI 10 (an older A/B variant may lack it)
         lib.nerf_mlp_h3_bytes.restype = ctypes.c_size_t
         lib.nerf_mlp_h3_bytes.argtypes = [c_i64]
@@ -293,7 +302,7 @@ def exported_symbols():
             "nerf_hash_encode_bwd_workspace_bytes",
             "nerf_quant_packed_bytes", "nerf_mlp_bwd_det_workspace_bytes", "nerf_priors_workspace_bytes",
             "nerf_normal_head_bwd_workspace_bytes", "nerf_active_rows_workspace_bytes",
-            "nerf_mlp_h3_bytes"] + list(SIGNATURES)
+            "nerf_mlp_h3_bytes", "nerf_occ_compact_workspace_bytes"] + list(SIGNATURES)
 
 
 _TIMING = None   # when a list: (name, start_event, end_event) per launch, recorded on the current stream

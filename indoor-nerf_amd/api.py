@@ -7,6 +7,7 @@ from .hashgrid import HashEmbedder, SHEncoder, fused_table_step_enabled, level_r
 from .losses import sigma_sparsity_loss, total_variation_all, total_variation_loss, train_loss
 from .model import (acaq_quantizers, acaq_update, create_nerf, make_args, save_checkpoint, structural_overfit_update,
                     train_step)
+from .occupancy import OccupancyGrid
 from .optim import RAdam
 from .quantization import FakeQuantizer, LearnedBitwidthQuantizer, PassthroughQuantizer, calculate_fqr
 from .rays import RaySampler, crop_window
@@ -31,7 +32,7 @@ __all__ = ["HashEmbedder", "SHEncoder", "NeRFSmall", "RAdam", "run_network", "ba
            "structured_planarity_loss", "set_deterministic", "deterministic", "check_numerics", "set_debug",
            "set_coarse_reuse", "coarse_reuse", "set_fused_coarse_sampler", "fused_coarse_sampler",
            "set_batched_composite_bwd", "batched_composite_bwd", "set_sh_rows", "sh_rows", "set_active_points", "active_points", "set_fused_table_step",
-           "fused_table_step_enabled"]
+           "fused_table_step_enabled", "OccupancyGrid"]
 
 
 def load_library():

@@ -647,6 +647,11 @@ def batchify(fn, chunk):
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):
     """run_nerf.py:53-68. inputs [..., S, 3], viewdirs [R, 3]. Fused when the modules are ours;
     netchunk is then only a memory knob the fused kernels do not need."""
+    occ = getattr(inputs, "_nerf_occupancy", None)   # render._OccupancyRequest of this render_rays call
+    if occ is not None:
+        from .occupancy import run_network_occupancy
+        occ.used = True
+        return run_network_occupancy(inputs, viewdirs, fn, embed_fn, embeddirs_fn, occ.grid)
     fused = (isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall)
              and isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3)
     if fused:

@@ -1,0 +1,203 @@
+"""Occupancy grid of the scene box: empty-space skipping for forward-only rendering.
+
+A density bitfield over the scene box, built from the trained field (OccupancyGrid.update), and the
+field call render_rays makes with one (run_network_occupancy): the kept samples — inside the box and in
+an occupied cell — are compacted in ascending order (csrc/occupancy.hip), hash-encoded and run through
+the MLP, whose results land in their rows of raw; every skipped sample gets an all-zero raw row.
+Compositing gives a sample with relu(sigma) = 0 weight 0 exactly, so skipping a sample the dense path
+would have given relu(sigma) = 0 changes nothing, and skipping any other equals masking sigma there.
+
+    grid = OccupancyGrid(args.bounding_box)              # after training / loading a checkpoint
+    grid.update(render_kwargs_test["embed_fn"], [render_kwargs_test["network_fn"],
+                                                 render_kwargs_test["network_fine"]])
+    render_kwargs_test["occupancy"] = grid                # render / render_path skip empty space
+
+Forward-only: no gradients, no raw noise, no normals head, no A-CAQ (render_rays and
+run_network_occupancy raise ValueError otherwise). The grid is not used in training and is not stored
+in checkpoints.
+"""
+import numpy as np
+import torch
+
+from . import _lib
+from .hashgrid import HashEmbedder, SHEncoder, _bbox_floats
+
+MAX_RESOLUTION = 1024   # res^3 cell ids fit 32 bits (csrc/occupancy.hip)
+
+
+def _check_modules(embed_fn, fn):
+    """The field the occupancy kernels can run: fp32 tables and plain MLP weights."""
+    from .field import NeRFSmall
+    if not isinstance(embed_fn, HashEmbedder) or not isinstance(fn, NeRFSmall):
+        raise ValueError("occupancy: needs the fused field modules (HashEmbedder + NeRFSmall), got "
+                         f"{type(embed_fn).__name__} + {type(fn).__name__}")
+    if embed_fn.use_quantization or fn.use_quantization:
+        raise ValueError("occupancy: A-CAQ quantizers are not supported (fp32 tables and weights only: the "
+                         "activation calibration depends on which points come first)")
+
+
+class OccupancyGrid:
+    """Density bitfield over `bounding_box`: resolution^3 cells, cell (ix, iy, iz) = bit
+    (ix*res + iy)*res + iz (csrc/occupancy.hip has the cell rule). A new grid is empty."""
+
+    def __init__(self, bounding_box, resolution=128, device=None):
+        res = int(resolution)
+        if not 1 <= res <= MAX_RESOLUTION:
+            raise ValueError(f"OccupancyGrid: resolution must be 1..{MAX_RESOLUTION}, got {resolution}")
+        bmin, bmax = _bbox_floats(bounding_box)
+        self.bounding_box = bounding_box
+        self.resolution = res
+        self.n_cells = res ** 3
+        self.n_words = (self.n_cells + 31) // 32
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self._bmin, self._bmax = _lib.host_f32(bmin), _lib.host_f32(bmax)
+        self.bits = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
+        self._last = (0, 0)
+
+    def _bits(self, t=None):
+        return _lib.ptr(self.bits if t is None else t, "occupancy bits", torch.int32)
+
+    # ---- bitfield <-> bool[res, res, res] ---------------------------------------------------
+    def set_mask(self, mask):
+        """Set the grid from a bool [res, res, res] array or tensor (True = occupied)."""
+        m = mask.detach().cpu().numpy() if torch.is_tensor(mask) else np.asarray(mask)
+        res = self.resolution
+        if m.shape != (res, res, res):
+            raise ValueError(f"OccupancyGrid.set_mask: mask must be [{res}, {res}, {res}], got {tuple(m.shape)}")
+        flat = np.zeros(32 * self.n_words, np.uint8)
+        flat[:self.n_cells] = m.reshape(-1).astype(bool)
+        words = np.packbits(flat, bitorder="little").view("<u4").astype(np.uint32)
+        self.bits.copy_(torch.from_numpy(words.view(np.int32)))
+
+    def mask(self):
+        """The grid as a bool [res, res, res] tensor on its device."""
+        words = self.bits.cpu().numpy().view(np.uint32).astype("<u4")
+        flat = np.unpackbits(words.view(np.uint8), bitorder="little")[:self.n_cells]
+        res = self.resolution
+        return torch.from_numpy(flat.astype(bool).reshape(res, res, res)).to(self.device)
+
+    def occupied_fraction(self):
+        return float(self.mask().float().mean())
+
+    def last_counts(self):
+        """(points evaluated, points total) of the most recent field call through this grid."""
+        return self._last
+
+    # ---- kernels ------------------------------------------------------------------------------
+    def query(self, pts):
+        """bool [...]: the point of pts [..., 3] is inside the box and its cell is occupied."""
+        p = pts.detach().reshape(-1, 3).float().contiguous()
+        out = torch.empty(p.shape[0], dtype=torch.bool, device=p.device)
+        _lib.call("nerf_occ_query", _lib.ptr(p, "pts"), p.shape[0], self._bmin, self._bmax, self.resolution,
+                  self._bits(), _lib.ptr(out, "out", torch.bool), _lib.stream())
+        return out.reshape(pts.shape[:-1])
+
+    def cell_points(self, cell_begin, n_cells, samples_per_cell, seed):
+        """[n_cells, samples_per_cell, 3]: the builder's sample positions of cells [cell_begin, +n_cells)
+        (sample 0 the centre, the others uniform in the cell; the same for any chunking)."""
+        pts = torch.empty(n_cells, samples_per_cell, 3, device=self.device, dtype=torch.float32)
+        _lib.call("nerf_occ_cell_points", self._bmin, self._bmax, self.resolution, int(cell_begin), int(n_cells),
+                  int(samples_per_cell), int(seed), 0, _lib.ptr(pts, "pts"), _lib.stream())
+        return pts
+
+    def update(self, embed_fn, networks, sigma_thresh=0.0, samples_per_cell=8, dilate=1, seed=0,
+               chunk_cells=1 << 17):
+        """Rebuild the grid from the field: a cell is occupied when sigma > sigma_thresh at any of its
+        samples_per_cell positions under any of `networks` (a NeRFSmall or a list: network_fn and
+        network_fine union into one grid), then dilated `dilate` times by one cell. Walks the cells in
+        chunks of chunk_cells (a multiple of 64; ~1.3 KB of scratch per cell at 8 samples)."""
+        from .field import NeRFSmall, _weights_struct
+        nets = [networks] if isinstance(networks, NeRFSmall) else [n for n in networks if n is not None]
+        nets = [n for i, n in enumerate(nets) if all(n is not m for m in nets[:i])]
+        for net in nets:
+            _check_modules(embed_fn, net)
+        if not nets:
+            raise ValueError("OccupancyGrid.update: no network")
+        if chunk_cells < 64 or chunk_cells % 64:
+            raise ValueError(f"OccupancyGrid.update: chunk_cells must be a positive multiple of 64, got {chunk_cells}")
+        spc, res, dev = int(samples_per_cell), self.resolution, self.device
+        L = embed_fn.n_levels
+        view = torch.tensor([[0.0, 0.0, 1.0]], device=dev)      # sigma does not depend on the view direction
+        with torch.no_grad():
+            self.bits.zero_()
+            for c0 in range(0, self.n_cells, chunk_cells):
+                nc = min(chunk_cells, self.n_cells - c0)
+                n = nc * spc
+                pts = self.cell_points(c0, nc, spc, seed).view(n, 3)
+                feat = torch.empty(L, n, 2, device=dev, dtype=torch.float32)
+                keep = torch.empty(n, device=dev, dtype=torch.bool)
+                embed_fn.encode_into(pts, feat, 2, 2 * n, keep)
+                raw = torch.empty(n, 4, device=dev, dtype=torch.float32)
+                for net in nets:
+                    _lib.call("nerf_mlp_fwd", _lib.ptr(feat, "feat"), 2, 2 * n, None, 0, _lib.ptr(view, "viewdirs"), n,
+                              _lib.ptr(keep, "keep", torch.bool), n, _weights_struct(net.mlp_weights()),
+                              _lib.ptr(raw, "raw"), None, _lib.stream())
+                    _lib.call("nerf_occ_mark", _lib.ptr(raw, "raw"), res, c0, nc, spc, float(sigma_thresh),
+                              self._bits(), _lib.stream())
+            for _ in range(int(dilate)):
+                out = torch.empty_like(self.bits)
+                _lib.call("nerf_occ_dilate", self._bits(), res, self._bits(out), _lib.stream())
+                self.bits = out
+        return self
+
+    def compact(self, pts, viewdirs, samples_per_ray, raw):
+        """The kept points of a field call over pts [P, 3] (point p on ray p // samples_per_ray):
+        (rows int32 [n] ascending, pts_c [n, 3], sh_c [n, 16]); the rows of raw [P, 4] of the skipped
+        points are zeroed. One host read (the count) between the two launches sizes the outputs."""
+        P, dev = pts.shape[0], pts.device
+        sh_rays = getattr(viewdirs, "_nerf_sh", None)
+        i32 = dict(device=dev, dtype=torch.int32)
+        count = torch.empty(1, **i32)
+        ws = torch.empty(int(_lib.load().nerf_occ_compact_workspace_bytes(P)) // 4, **i32)
+
+        def run(stages, cap, rows, pts_c, sh_c):
+            _lib.call("nerf_occ_compact", _lib.ptr(pts, "pts"), P, _lib.ptr(sh_rays, "sh_rows", allow_none=True),
+                      None if sh_rays is not None else _lib.ptr(viewdirs, "viewdirs"), samples_per_ray,
+                      self._bmin, self._bmax, self.resolution, self._bits(), stages, cap,
+                      _lib.ptr(rows, "rows", torch.int32, True), _lib.ptr(count, "count", torch.int32),
+                      _lib.ptr(pts_c, "pts_c", allow_none=True), _lib.ptr(sh_c, "sh_c", allow_none=True),
+                      _lib.ptr(raw, "raw"), _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+        run(1, 0, None, None, None)
+        n = int(count.item())
+        f = dict(device=dev, dtype=torch.float32)
+        rows, pts_c, sh_c = torch.empty(n, **i32), torch.empty(n, 3, **f), torch.empty(n, 16, **f)
+        if P > 0:
+            run(2, n, rows if n else None, pts_c if n else None, sh_c if n else None)
+        self._last = (n, P)
+        return rows, pts_c, sh_c
+
+
+def run_network_occupancy(inputs, viewdirs, fn, embed_fn, embeddirs_fn, grid):
+    """run_network (field.py) through an occupancy grid: inputs [R, S, 3], viewdirs [R, 3] ->
+    raw [R, S, 4] with the field evaluated at the kept samples only and zero rows elsewhere."""
+    from .field import _point_order, _weights_struct
+    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 3:
+        raise ValueError("occupancy: needs the fused field call (SHEncoder view encoding, viewdirs, inputs [R, S, 3])")
+    _check_modules(embed_fn, fn)
+    if fn.raw_channels != 4:
+        raise ValueError("occupancy: a normals head is not supported (run_network's box mask then lands on n_z, "
+                         "not on sigma, so a skipped sample is not a zero-weight sample)")
+    if torch.is_grad_enabled():
+        raise ValueError("occupancy: forward-only (call under torch.no_grad(); the grid is not used in training)")
+    if embed_fn.training:
+        embed_fn.current_step += 1
+    R, S = inputs.shape[0], inputs.shape[1]
+    P, dev = R * S, inputs.device
+    if 16 * (P + 32) >= 2 ** 31:
+        raise ValueError(f"occupancy: {P} points per field call exceed the MLP's 32-bit row indexing; use a smaller chunk")
+    pts = inputs.detach().reshape(-1, 3).float().contiguous()
+    sh_rays = getattr(viewdirs, "_nerf_sh", None)
+    viewdirs = viewdirs.detach().float().contiguous()
+    if sh_rays is not None:
+        viewdirs._nerf_sh = sh_rays
+    raw = torch.empty(P, 4, device=dev, dtype=torch.float32)
+    rows, pts_c, sh_c = grid.compact(pts, viewdirs, S, raw)
+    n = rows.shape[0]
+    if n > 0:
+        feat = torch.empty(embed_fn.n_levels, n, 2, device=dev, dtype=torch.float32)
+        keep = torch.empty(n, device=dev, dtype=torch.bool)
+        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep)
+        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * n, _lib.ptr(sh_c, "sh_c"), 16, None, 1,
+                  _lib.ptr(keep, "keep", torch.bool), n, _weights_struct(fn.mlp_weights()), _lib.ptr(raw, "raw"),
+                  None, None, None, 0, _point_order((rows, 0, 0)), _lib.stream())
+    return raw.reshape(R, S, 4)

@@ -374,10 +374,38 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return out
 
 
+class _OccupancyRequest:
+    """render_rays' occupancy grid on its way to the fused run_network (attached to the point tensor as
+    `pts._nerf_occupancy`); `used` tells render_rays that the query function took the occupancy path."""
+
+    def __init__(self, grid):
+        self.grid, self.used = grid, False
+
+
+def _query(network_query_fn, pts, viewdirs, fn, occupancy):
+    if occupancy is None:
+        return network_query_fn(pts, viewdirs, fn)
+    req = pts._nerf_occupancy = _OccupancyRequest(occupancy)
+    raw = network_query_fn(pts, viewdirs, fn)
+    del pts._nerf_occupancy
+    if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
+        raise ValueError("render_rays: occupancy needs a network_query_fn that calls this package's run_network")
+    return raw
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False, lindisp=False,
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
-                pytest=False, predict_normals=False):
-    """run_nerf.py:414-549."""
+                pytest=False, predict_normals=False, occupancy=None):
+    """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
+    the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
+    all-zero raw row (weight 0). None (the default) is the dense path."""
+    if occupancy is not None:
+        if torch.is_grad_enabled():
+            raise ValueError("render_rays: occupancy is forward-only (call under torch.no_grad(); the grid is not "
+                             "used in training)")
+        if raw_noise_std > 0.:
+            raise ValueError("render_rays: occupancy needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
+                             "at skipped samples)")
     rays = ray_batch.detach().float().contiguous()
     R, C = rays.shape
     dev = rays.device
@@ -403,10 +431,12 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if sh_rays is not None:
         viewdirs._nerf_sh = sh_rays
 
-    reuse = CoarseReuse(R, N_samples, N_importance) if (N_importance > 0 and _REUSE["on"] and R > 0) else None
+    # coarse-feature reuse is off with an occupancy grid (each pass encodes its own kept points)
+    reuse = (CoarseReuse(R, N_samples, N_importance)
+             if (N_importance > 0 and _REUSE["on"] and R > 0 and occupancy is None) else None)
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
-    raw = network_query_fn(pts, viewdirs, network_fn)
+    raw = _query(network_query_fn, pts, viewdirs, network_fn, occupancy)
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -446,7 +476,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         run_fn = network_fn if network_fine is None else network_fine
         if reuse is not None:
             pts._nerf_reuse = reuse
-        raw = network_query_fn(pts, viewdirs, run_fn)
+        raw = _query(network_query_fn, pts, viewdirs, run_fn, occupancy)
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()

@@ -1,0 +1,188 @@
+"""Measurement (GPU box): forward-only render time of one 800 x 800 frame of the trained two-sphere
+scene (tests/test_gpu_converge.py's setup, 64 coarse + 128 importance samples, chunk 32768), dense and
+through an occupancy grid (occupancy.OccupancyGrid).
+
+Dense and grid frames alternate in one process after a warm-up of both; each frame sits between two
+device events and ends in a synchronise. Also reported: the grid's build time, its occupied fraction,
+the share of the points each pass evaluates and the PSNR of every render against the procedural target.
+Besides the grid of update()'s defaults the same frame is timed through grids of other builder settings,
+through a grid with every cell set (the path's overhead when nothing inside the box is skipped: two
+compaction launches and one 4-byte read of the count per field call, and no coarse-feature reuse) and
+through the grid of the scene's own geometry (what a converged field's grid would approach).
+
+usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
+"""
+import argparse
+import ast
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+import indoor_nerf_amd as nerf  # noqa: E402
+from tables import (SCENE_SPHERES, blender_bbox, closed_form_table, convergence_rays, pose_spherical,  # noqa: E402
+                    procedural_targets)
+
+
+def trained_scene(iters=300):
+    """The two-sphere scene of tests/test_gpu_converge.py trained `iters` iterations on seeded batches:
+    (bbox, embedder, coarse net, fine net, render kwargs for evaluation)."""
+    if not torch.cuda.is_available():
+        raise SystemExit("render_time: needs a GPU (a time measured elsewhere says nothing)")
+    gpu = torch.device("cuda:0")
+    g = np.load(os.path.join(ROOT, "tests", "golden", "f19_converge.npz"))
+    c = ast.literal_eval(str(g["config"]))
+    lo, hi = blender_bbox()
+    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
+    emb = nerf.HashEmbedder(bbox, finest_resolution=1024).to(gpu)
+    table = closed_form_table(scale=c["table_scale"], salt=c["table_salt"])
+
+    def net(prefix):
+        m = nerf.NeRFSmall(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
+                           input_ch=32, input_ch_views=16).to(gpu)
+        with torch.no_grad():
+            for k, p in m.named_parameters():
+                p.copy_(torch.from_numpy(g[prefix + k.replace(".", "_")]))
+        return m
+
+    coarse, fine = net("coarse0_"), net("fine0_")
+    with torch.no_grad():
+        for i, e in enumerate(emb.embeddings):
+            e.weight.copy_(torch.from_numpy(table[i]))
+    sh = nerf.SHEncoder()
+    nqf = lambda inputs, viewdirs, fn: nerf.run_network(inputs, viewdirs, fn, emb, sh)  # noqa: E731
+    kw = dict(network_query_fn=nqf, perturb=1.0, N_importance=128, network_fine=fine, N_samples=64,
+              network_fn=coarse, embed_fn=emb, use_viewdirs=True, white_bkgd=True, raw_noise_std=0.0,
+              predict_normals=False, ndc=False, lindisp=False, near=2.0, far=6.0, pytest=True)
+    kw_test = dict(kw, perturb=0.0, pytest=False)
+    args = nerf.make_args(lrate=c["lrate"], lrate_decay=c["lrate_decay"], sparse_loss_weight=c["sparsity"],
+                          tv_loss_weight=0.0, N_samples=64, N_importance=128, white_bkgd=True)
+    (ro, rd, rgb), _, _ = convergence_rays()
+    ro, rd, rgb = (torch.from_numpy(x).to(gpu) for x in (ro, rd, rgb))
+    opt = nerf.RAdam([{"params": list(coarse.parameters()) + list(fine.parameters()), "weight_decay": 1e-6},
+                      {"params": list(emb.parameters()), "eps": 1e-15}], lr=c["lrate"], betas=(0.9, 0.99))
+    rng = np.random.RandomState(100)
+    for it in range(1, iters + 1):
+        idx = torch.from_numpy(rng.choice(ro.shape[0], c["R"], replace=False).astype(np.int64)).to(gpu)
+        nerf.train_step((ro[idx], rd[idx]), rgb[idx], kw, opt, args, it)
+    for m in (coarse, fine, emb):
+        m.eval()
+
+    return bbox, emb, coarse, fine, kw_test
+
+
+def geometry_mask(lo, hi, res):
+    """Cells of the procedural scene itself: those whose centre lies within a sphere's radius plus one
+    cell diagonal of its centre (tables.SCENE_SPHERES) — the grid a converged field would approach."""
+    cell = (hi - lo) / res
+    axes = [lo[a] + (np.arange(res) + 0.5) * cell[a] for a in range(3)]
+    x, y, z = np.meshgrid(*axes, indexing="ij")
+    mask = np.zeros((res, res, res), bool)
+    for c, r in SCENE_SPHERES:
+        mask |= np.sqrt((x - c[0]) ** 2 + (y - c[1]) ** 2 + (z - c[2]) ** 2) <= r + float(np.linalg.norm(cell))
+    return mask
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--frames", type=int, default=10)
+    ap.add_argument("--iters", type=int, default=300)
+    ap.add_argument("--size", type=int, default=800)
+    ap.add_argument("--chunk", type=int, default=32768)
+    ap.add_argument("--resolution", type=int, default=128)
+    ap.add_argument("--out", default="bench_out/render_time.json")
+    a = ap.parse_args()
+    bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
+    gpu = torch.device("cuda:0")
+    lo, hi = blender_bbox()
+    new_grid = lambda: nerf.OccupancyGrid(bbox, resolution=a.resolution, device=gpu)  # noqa: E731
+
+    # the grid with update()'s defaults, and its build time (the first build includes first-launch costs)
+    grids = {"grid": new_grid()}
+    build_ms = []
+    for _ in range(3):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        grids["grid"].update(emb, [coarse, fine])
+        torch.cuda.synchronize()
+        build_ms.append(1e3 * (time.perf_counter() - t0))
+    # other builder settings (sigma_thresh, dilate), every cell set (the path's overhead when nothing inside
+    # the box is skipped), and the scene's own geometry (what a converged field's grid would approach)
+    for th, dil in ((0.0, 0), (0.1, 1), (0.3, 1)):
+        grids[f"grid_thresh{th:g}_dilate{dil}"] = new_grid().update(emb, [coarse, fine], sigma_thresh=th, dilate=dil)
+    grids["full_grid"] = new_grid()
+    grids["full_grid"].set_mask(np.ones((a.resolution,) * 3, bool))
+    grids["geometry_grid"] = new_grid()
+    grids["geometry_grid"].set_mask(geometry_mask(lo, hi, a.resolution))
+
+    H = W = a.size
+    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
+    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
+    pose = torch.from_numpy(pose_spherical(np.linspace(-180, 180, 101)[34], -30.0, 4.0311))[:3, :4].to(gpu)
+
+    def frame(occupancy):
+        with torch.no_grad():
+            return nerf.render(H, W, K, chunk=a.chunk, c2w=pose, **dict(kw_test, occupancy=occupancy))[0]
+
+    def timed(occupancy):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        frame(occupancy)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    # PSNR of every render against the procedural target of the same rays
+    ro_np, rd_np = nerf.get_rays_np(H, W, K, pose.cpu().numpy())
+    target = torch.from_numpy(procedural_targets(np.ascontiguousarray(ro_np.reshape(-1, 3), np.float32),
+                                                 np.ascontiguousarray(rd_np.reshape(-1, 3), np.float32))).to(gpu)
+    psnr = lambda img: float(-10.0 * torch.log10(((img.reshape(-1, 3) - target) ** 2).mean()))  # noqa: E731
+    report = {"dense": {"psnr_db": psnr(frame(None))}}
+
+    # evaluated share per pass: one untimed frame per grid with the compaction's counts recorded
+    for name, grid in grids.items():
+        calls = []
+        compact = grid.compact
+
+        def recording(pts, viewdirs, spr, raw, grid=grid, compact=compact, calls=calls):
+            out = compact(pts, viewdirs, spr, raw)
+            calls.append((spr,) + grid.last_counts())
+            return out
+        grid.compact = recording
+        img = frame(grid)
+        del grid.compact
+        share = {}
+        for pname, spr in (("coarse", 64), ("fine", 192)):
+            n, P = sum(k[1] for k in calls if k[0] == spr), sum(k[2] for k in calls if k[0] == spr)
+            share[pname] = {"evaluated": n, "points": P, "share": n / max(1, P)}
+        report[name] = {"psnr_db": psnr(img), "occupied_fraction": grid.occupied_fraction(), "evaluated": share,
+                        "count_reads_per_frame": len(calls)}
+
+    variants = [("dense", None)] + list(grids.items())
+    for _, occ in variants:             # warm-up of every variant
+        timed(occ)
+    times = {name: [] for name, _ in variants}
+    for _ in range(a.frames):           # alternating
+        for name, occ in variants:
+            times[name].append(timed(occ))
+    for name, v in times.items():
+        report[name]["render_ms"] = {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)),
+                                     "frames": len(v)}
+        report[name]["speedup_vs_dense"] = float(np.median(times["dense"]) / np.median(v))
+    out = {"scene": f"two-sphere scene, {a.iters} training iterations", "frame": [H, W], "chunk": a.chunk,
+           "N_samples": 64, "N_importance": 128, "grid_resolution": a.resolution,
+           "grid_build_ms": build_ms, "variants": report, "device": torch.cuda.get_device_name(0)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fp:
+        json.dump(out, fp, indent=1)
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
