@@ -806,6 +806,35 @@ int nerf_occ_compact(const float* d_pts, int64_t n_points, const float* d_sh_ray
                      float* d_pts_c, float* d_sh_c, float* d_raw, void* d_workspace, size_t workspace_bytes,
                      void* stream);
 
+/* ---- early ray termination for forward-only rendering (csrc/early_stop.hip) ----------------------
+ * Additive entries (the ABI version stays 12). A field call over d_pts [n_rays, samples_per_ray, 3]
+ * (point p = r * samples_per_ray + s) runs front to back in slabs [s0, s1) of samples.
+ *
+ * nerf_ert_compact: the kept points of one slab, 0 <= s0 <= s1 <= samples_per_ray. The n_rays * (s1 - s0)
+ *   candidates are enumerated ray-major, so the kept list is ascending in p. A candidate is kept when
+ *   d_alive[r] != 0 (uint8 [n_rays]; NULL: every ray is alive), the point lies inside the box and, with
+ *   d_bits non-NULL, the bit of its cell in the res^3 occupancy grid is set (nerf_occ_*'s cell rule; res
+ *   is ignored without d_bits). `stages`, capacity, d_rows, d_counts, d_pts_c, d_sh_c, d_sh_rays /
+ *   d_viewdirs and the workspace (nerf_ert_compact_workspace_bytes(n_rays * (s1 - s0))) are
+ *   nerf_occ_compact's; d_rows holds indices into [n_rays * samples_per_ray]. The scatter stage zeroes
+ *   the row of d_raw [n_rays * samples_per_ray, 4] of every candidate it does not keep (every sample of
+ *   a dead ray included) and touches no row outside the slab.
+ * nerf_ert_advance: after the field has run on slab [s0, s1), s1 < samples_per_ray: for every ray with
+ *   d_alive[r] != 0, in fp32 and in sample order (no fused multiply-add),
+ *   norm = sqrtf(dx*dx + dy*dy + dz*dz) of d_rays_d [n_rays, 3]; for i in [s0, s1):
+ *   d_tau[r] += max(sigma_i, 0) * ((z[i+1] - z[i]) * norm) with sigma_i = d_raw[p, 3] (NaN counts as 0)
+ *   and z = d_z [n_rays, samples_per_ray]; then, if d_tau[r] > tau_max: d_alive[r] = 0, d_stop[r] = s1
+ *   (int32). Rays already dead are left untouched. */
+size_t nerf_ert_compact_workspace_bytes(int64_t n_candidates);
+int nerf_ert_compact(const float* d_pts, int64_t n_rays, int64_t samples_per_ray, int64_t s0, int64_t s1,
+                     const uint8_t* d_alive, const float* d_sh_rays, const float* d_viewdirs, const float* bbox_min,
+                     const float* bbox_max, int res, const uint32_t* d_bits, int stages, int64_t capacity,
+                     int32_t* d_rows, int32_t* d_counts, float* d_pts_c, float* d_sh_c, float* d_raw,
+                     void* d_workspace, size_t workspace_bytes, void* stream);
+int nerf_ert_advance(const float* d_raw, const float* d_z, const float* d_rays_d, int64_t n_rays,
+                     int64_t samples_per_ray, int64_t s0, int64_t s1, float tau_max, float* d_tau, uint8_t* d_alive,
+                     int32_t* d_stop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

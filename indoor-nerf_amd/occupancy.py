@@ -25,14 +25,14 @@ from .hashgrid import HashEmbedder, SHEncoder, _bbox_floats
 MAX_RESOLUTION = 1024   # res^3 cell ids fit 32 bits (csrc/occupancy.hip)
 
 
-def _check_modules(embed_fn, fn):
+def _check_modules(embed_fn, fn, what="occupancy"):
     """The field the occupancy kernels can run: fp32 tables and plain MLP weights."""
     from .field import NeRFSmall
     if not isinstance(embed_fn, HashEmbedder) or not isinstance(fn, NeRFSmall):
-        raise ValueError("occupancy: needs the fused field modules (HashEmbedder + NeRFSmall), got "
+        raise ValueError(f"{what}: needs the fused field modules (HashEmbedder + NeRFSmall), got "
                          f"{type(embed_fn).__name__} + {type(fn).__name__}")
     if embed_fn.use_quantization or fn.use_quantization:
-        raise ValueError("occupancy: A-CAQ quantizers are not supported (fp32 tables and weights only: the "
+        raise ValueError(f"{what}: A-CAQ quantizers are not supported (fp32 tables and weights only: the "
                          "activation calibration depends on which points come first)")
 
 

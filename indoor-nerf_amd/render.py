@@ -382,23 +382,56 @@ class _OccupancyRequest:
         self.grid, self.used = grid, False
 
 
-def _query(network_query_fn, pts, viewdirs, fn, occupancy):
+def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None):
+    """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
+    (stops int32 [R], early_stop.py), None otherwise (stops None)."""
+    if early is not None:
+        from .early_stop import EarlyStopRequest
+        req = pts._nerf_early_stop = EarlyStopRequest(*early, grid=occupancy)
+        raw = network_query_fn(pts, viewdirs, fn)
+        del pts._nerf_early_stop
+        if not req.used:   # as below: never fall back to the dense path silently
+            raise ValueError("render_rays: early_stop needs a network_query_fn that calls this package's run_network")
+        return raw, req.stop
     if occupancy is None:
-        return network_query_fn(pts, viewdirs, fn)
+        return network_query_fn(pts, viewdirs, fn), None
     req = pts._nerf_occupancy = _OccupancyRequest(occupancy)
     raw = network_query_fn(pts, viewdirs, fn)
     del pts._nerf_occupancy
     if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
         raise ValueError("render_rays: occupancy needs a network_query_fn that calls this package's run_network")
-    return raw
+    return raw, None
+
+
+def last_early_stop_counts():
+    """(points evaluated, points total) of the most recent field call with early_stop, summed over its
+    slabs (the analogue of OccupancyGrid.last_counts())."""
+    from .early_stop import last_counts
+    return last_counts()
 
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False, lindisp=False,
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
-                pytest=False, predict_normals=False, occupancy=None):
+                pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
-    all-zero raw row (weight 0). None (the default) is the dense path."""
+    all-zero raw row (weight 0). None (the default) is the dense path.
+    early_stop (a transmittance threshold 0 < eps < 1; forward-only rendering): each pass
+    runs front to back in slabs of early_stop_slab samples and a ray whose optical depth has passed
+    -log(eps) gets all-zero raw rows in every later slab; the result then also holds early_stop_samples
+    (int32 [R], the leading samples of the final pass for which the ray was alive) and, with
+    N_importance > 0, early_stop_samples0 (the coarse pass). Composes with occupancy. None (the default)
+    leaves the call as it is without it."""
+    early = None
+    if early_stop is not None:
+        from .early_stop import check_params
+        early = check_params(early_stop, early_stop_slab)
+        if torch.is_grad_enabled():
+            raise ValueError("render_rays: early_stop is forward-only (call under torch.no_grad(); rays are not "
+                             "stopped in training)")
+        if raw_noise_std > 0.:
+            raise ValueError("render_rays: early_stop needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
+                             "at skipped samples)")
     if occupancy is not None:
         if torch.is_grad_enabled():
             raise ValueError("render_rays: occupancy is forward-only (call under torch.no_grad(); the grid is not "
@@ -431,12 +464,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if sh_rays is not None:
         viewdirs._nerf_sh = sh_rays
 
-    # coarse-feature reuse is off with an occupancy grid (each pass encodes its own kept points)
+    # coarse-feature reuse is off with an occupancy grid or early termination (each pass encodes its own kept points)
     reuse = (CoarseReuse(R, N_samples, N_importance)
-             if (N_importance > 0 and _REUSE["on"] and R > 0 and occupancy is None) else None)
+             if (N_importance > 0 and _REUSE["on"] and R > 0 and occupancy is None and early is None) else None)
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
-    raw = _query(network_query_fn, pts, viewdirs, network_fn, occupancy)
+    raw, stops = _query(network_query_fn, pts, viewdirs, network_fn, occupancy,
+                        None if early is None else (z, rays_d) + early)
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -476,7 +510,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         run_fn = network_fn if network_fine is None else network_fine
         if reuse is not None:
             pts._nerf_reuse = reuse
-        raw = _query(network_query_fn, pts, viewdirs, run_fn, occupancy)
+        stops0 = stops
+        raw, stops = _query(network_query_fn, pts, viewdirs, run_fn, occupancy,
+                            None if early is None else (z, rays_d) + early)
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()
@@ -486,6 +522,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         rgb_map, disp_map, acc_map, weights, depth_map, sparsity_loss = outs[:6]
         normal_map = outs[6] if predict_normals else None
         ret.update(rgb0=rgb_map_0, depth0=depth_map_0, acc0=acc_map_0, sparsity_loss0=sparsity_loss_0, z_std=z_std)
+        if early is not None:
+            ret["early_stop_samples0"] = stops0
         if predict_normals:
             ret["normal0"] = normal_map_0
     else:
@@ -498,6 +536,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                rays_d=rays_d)
     if predict_normals:
         ret["normal_map"] = normal_map
+    if early is not None:
+        ret["early_stop_samples"] = stops
     if retraw:
         ret["raw"] = _RawGuardFn.apply(raw) if getattr(raw, "_nerf_field_raw", False) else raw
     if DEBUG:

@@ -10,7 +10,15 @@ through a grid with every cell set (the path's overhead when nothing inside the 
 compaction launches and one 4-byte read of the count per field call, and no coarse-feature reuse) and
 through the grid of the scene's own geometry (what a converged field's grid would approach).
 
+With --early-stop the same frame, process and method time early ray termination instead (early_stop.py,
+DESIGN.md §14): early_stop in {1e-2, 1e-3} x early_stop_slab in {16, 32, 64}, each without a grid, with
+the grid of update()'s defaults and with the scene's own geometry grid, and per slab size a row with a
+threshold so small that nothing terminates (1e-300: the path's pure overhead — the compaction of every
+slab, one 4-byte read of the count per slab, no coarse-feature reuse). The dense frame of the unchanged
+path is the baseline.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
+       python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
 """
 import argparse
 import ast
@@ -89,6 +97,92 @@ def geometry_mask(lo, hi, res):
     return mask
 
 
+def main_early_stop(a):
+    """The early-termination table: see the module docstring."""
+    bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
+    gpu = torch.device("cuda:0")
+    lo, hi = blender_bbox()
+    grids = {"no grid": None,
+             "default grid": nerf.OccupancyGrid(bbox, resolution=a.resolution, device=gpu).update(emb, [coarse, fine]),
+             "geometry grid": nerf.OccupancyGrid(bbox, resolution=a.resolution, device=gpu)}
+    grids["geometry grid"].set_mask(geometry_mask(lo, hi, a.resolution))
+
+    H = W = a.size
+    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
+    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
+    pose = torch.from_numpy(pose_spherical(np.linspace(-180, 180, 101)[34], -30.0, 4.0311))[:3, :4].to(gpu)
+
+    def frame(over, kw=kw_test):
+        with torch.no_grad():
+            return nerf.render(H, W, K, chunk=a.chunk, c2w=pose, **dict(kw, **over))
+
+    def timed(over):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        frame(over)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    ro_np, rd_np = nerf.get_rays_np(H, W, K, pose.cpu().numpy())
+    target = torch.from_numpy(procedural_targets(np.ascontiguousarray(ro_np.reshape(-1, 3), np.float32),
+                                                 np.ascontiguousarray(rd_np.reshape(-1, 3), np.float32))).to(gpu)
+    psnr = lambda img: float(-10.0 * torch.log10(((img.reshape(-1, 3) - target) ** 2).mean()))  # noqa: E731
+
+    variants = [("dense", {}, dict(early_stop=None, early_stop_slab=None, grid=None))]
+    for slab in (16, 32, 64):
+        variants.append((f"overhead (eps 1e-300), slab {slab}", dict(early_stop=1e-300, early_stop_slab=slab),
+                         dict(early_stop=1e-300, early_stop_slab=slab, grid="no grid")))
+    for gname, grid in grids.items():
+        for eps in (1e-2, 1e-3):
+            for slab in (16, 32, 64):
+                over = dict(early_stop=eps, early_stop_slab=slab, **({} if grid is None else {"occupancy": grid}))
+                variants.append((f"eps {eps:g}, slab {slab}, {gname}", over,
+                                 dict(early_stop=eps, early_stop_slab=slab, grid=gname)))
+
+    # PSNR, evaluated share per pass and count reads: one untimed frame per variant through a query function
+    # that records the counts of every field call (it passes the point tensor on untouched)
+    report = {}
+    nqf = kw_test["network_query_fn"]
+    for name, over, desc in variants:
+        calls = []
+
+        def recording(pts, viewdirs, fn, calls=calls, slab=desc["early_stop_slab"]):
+            raw = nqf(pts, viewdirs, fn)
+            if slab is not None:
+                calls.append((pts.shape[1], -(-pts.shape[1] // slab)) + nerf.last_early_stop_counts())
+            return raw
+        out = frame(over, dict(kw_test, network_query_fn=recording))
+        report[name] = dict(desc, psnr_db=psnr(out[0]))
+        if calls:
+            share = {}
+            for pname, spr in (("coarse", 64), ("fine", 192)):
+                n, P = sum(k[2] for k in calls if k[0] == spr), sum(k[3] for k in calls if k[0] == spr)
+                share[pname] = {"evaluated": n, "points": P, "share": n / max(1, P)}
+            report[name].update(evaluated=share, count_reads_per_frame=sum(k[1] for k in calls),
+                                alive_samples_mean={"coarse": float(out[3]["early_stop_samples0"].float().mean()),
+                                                    "fine": float(out[3]["early_stop_samples"].float().mean())})
+
+    for _, over, _ in variants:         # warm-up of every variant
+        timed(over)
+    times = {name: [] for name, _, _ in variants}
+    for _ in range(a.frames):           # alternating
+        for name, over, _ in variants:
+            times[name].append(timed(over))
+    for name, v in times.items():
+        report[name]["render_ms"] = {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)),
+                                     "frames": len(v)}
+        report[name]["speedup_vs_dense"] = float(np.median(times["dense"]) / np.median(v))
+    out = {"scene": f"two-sphere scene, {a.iters} training iterations", "frame": [H, W], "chunk": a.chunk,
+           "N_samples": 64, "N_importance": 128, "grid_resolution": a.resolution,
+           "grid_occupied_fraction": {k: g.occupied_fraction() for k, g in grids.items() if g is not None},
+           "variants": report, "device": torch.cuda.get_device_name(0)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fp:
+        json.dump(out, fp, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -96,8 +190,13 @@ def main():
     ap.add_argument("--size", type=int, default=800)
     ap.add_argument("--chunk", type=int, default=32768)
     ap.add_argument("--resolution", type=int, default=128)
-    ap.add_argument("--out", default="bench_out/render_time.json")
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--early-stop", action="store_true", help="time early ray termination (DESIGN.md §14)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = "profiles/early_stop_render_time.json" if a.early_stop else "bench_out/render_time.json"
+    if a.early_stop:
+        return main_early_stop(a)
     bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
     gpu = torch.device("cuda:0")
     lo, hi = blender_bbox()
