@@ -835,6 +835,32 @@ int nerf_ert_advance(const float* d_raw, const float* d_z, const float* d_rays_d
                      int64_t samples_per_ray, int64_t s0, int64_t s1, float tau_max, float* d_tau, uint8_t* d_alive,
                      int32_t* d_stop, void* stream);
 
+/* ---- per-ray sample bounds from the occupancy grid (csrc/ray_span.hip) -----------------------------
+ * Additive entries (the ABI version stays 12), forward-only rendering. d_rays [n_rays, n_cols] are
+ * packed ray rows (nerf_rays_pack: o, d, near, far and, with n_cols = 11, the view direction; n_cols
+ * is 8 or 11); the box, res and d_bits are an occupancy grid as above, whose cells must also be at least
+ * 2^-10 of the box's largest |bound| per axis.
+ *
+ * nerf_ray_span: one 3-D DDA per ray through the grid, after a slab test against the box and the ray's
+ *   own [near, far] (csrc/ray_span.hip states the rule operation by operation; an axis with d = 0 takes
+ *   its cell from the cell rule above and misses when the origin is outside the box on it). With I the
+ *   depths of [near, far] at which o + t d is inside the box and in a cell whose bit is set:
+ *   d_hit[r] (uint8) = I is not empty, d_span[r] = {max(near, inf I - pad), min(far, sup I + pad)} with
+ *   pad = 2^-4 min over axes with d != 0 of cell / |d|; a ray whose span is empty after that is a miss,
+ *   and a missed ray gets d_span[r] = {near, far}. d_counts[0] (int32) = number of hit rays; the
+ *   workspace (nerf_ray_span_workspace_bytes(n_rays)) receives the counts per 4096 rays.
+ * nerf_ray_span_gather: d_rows[i] (int32) = the i-th hit ray (ascending) and d_rays_c [capacity, n_cols]
+ *   its row with columns 6 and 7 replaced by its span, for i < capacity <= n_rays; it reads d_hit, d_span
+ *   and the workspace as nerf_ray_span over the same rays left them.
+ * n_rays = 0 (and, for the gather, capacity = 0) launches nothing and accepts NULL buffers. */
+size_t nerf_ray_span_workspace_bytes(int64_t n_rays);
+int nerf_ray_span(const float* d_rays, int64_t n_rays, int n_cols, const float* bbox_min, const float* bbox_max,
+                  int res, const uint32_t* d_bits, uint8_t* d_hit, float* d_span, int32_t* d_counts,
+                  void* d_workspace, size_t workspace_bytes, void* stream);
+int nerf_ray_span_gather(const float* d_rays, int64_t n_rays, int n_cols, const uint8_t* d_hit, const float* d_span,
+                         int64_t capacity, int32_t* d_rows, float* d_rays_c, const void* d_workspace,
+                         size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

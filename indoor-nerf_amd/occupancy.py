@@ -166,6 +166,45 @@ class OccupancyGrid:
         self._last = (n, P)
         return rows, pts_c, sh_c
 
+    # ---- per-ray sample bounds (csrc/ray_span.hip) --------------------------------
+    def _span(self, rays):
+        if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] not in (8, 11):
+            raise ValueError("OccupancyGrid.ray_span: rays must be packed rows [R, 8] or [R, 11] (o, d, near, far"
+                             f"[, viewdir]), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}")
+        rays = rays.detach().float().contiguous()
+        R, C, dev = rays.shape[0], rays.shape[1], rays.device
+        hit = torch.empty(R, dtype=torch.bool, device=dev)
+        span = torch.empty(R, 2, dtype=torch.float32, device=dev)
+        count = torch.empty(1, dtype=torch.int32, device=dev)
+        ws = torch.empty(int(_lib.load().nerf_ray_span_workspace_bytes(R)) // 4, dtype=torch.int32, device=dev)
+        _lib.call("nerf_ray_span", _lib.ptr(rays, "rays"), R, C, self._bmin, self._bmax, self.resolution, self._bits(),
+                  _lib.ptr(hit, "hit", torch.bool), _lib.ptr(span, "span"), _lib.ptr(count, "count", torch.int32),
+                  _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+        return rays, hit, span, count, ws
+
+    def ray_span(self, rays):
+        """Where along each packed ray row [R, 8 or 11] (o, d, near, far[, viewdir]) there is anything:
+        (hit bool [R], span float32 [R, 2]). hit: the ray crosses an occupied cell inside [near, far];
+        span: from the first to the last such cell, widened by pad and clipped to [near, far]
+        ([near, far] itself for a missed ray)."""
+        _, hit, span, _, _ = self._span(rays)
+        return hit, span
+
+    def bound_rays(self, rays):
+        """ray_span and the hit rays compacted: (hit [R], span [R, 2], rows int32 [n] ascending,
+        rays_c [n, C] = the hit rows with columns 6 and 7 replaced by their spans). One host read (the
+        count) sizes the outputs."""
+        rays, hit, span, count, ws = self._span(rays)
+        R, C, dev = rays.shape[0], rays.shape[1], rays.device
+        n = int(count.item()) if R > 0 else 0
+        rows = torch.empty(n, dtype=torch.int32, device=dev)
+        rays_c = torch.empty(n, C, dtype=torch.float32, device=dev)
+        if n > 0:
+            _lib.call("nerf_ray_span_gather", _lib.ptr(rays, "rays"), R, C, _lib.ptr(hit, "hit", torch.bool),
+                      _lib.ptr(span, "span"), n, _lib.ptr(rows, "rows", torch.int32), _lib.ptr(rays_c, "rays_c"),
+                      _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+        return hit, span, rows, rays_c
+
 
 def run_network_occupancy(inputs, viewdirs, fn, embed_fn, embeddirs_fn, grid):
     """run_network (field.py) through an occupancy grid: inputs [R, S, 3], viewdirs [R, 3] ->

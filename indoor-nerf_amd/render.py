@@ -532,6 +532,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         rgb_map, disp_map, acc_map, weights, depth_map, sparsity_loss = outs[:6]
         normal_map = outs[6] if predict_normals else None
 
+    # the entries of ret, their shapes and dtypes are restated for zero rays in _no_rays_result (render's
+    # ray_bounds path, when no ray of a frame is hit): keep the two in step
     ret.update(rgb_map=rgb_map, depth_map=depth_map, acc_map=acc_map, sparsity_loss=sparsity_loss, pts=pts,
                rays_d=rays_d)
     if predict_normals:
@@ -622,9 +624,84 @@ def _pack_rays(H, W, K, rays_o, rays_d, near, far, ndc, use_viewdirs):
     return out
 
 
+def _missed_value(key, white_bkgd):
+    """What a ray that crosses no occupied cell gets in entry `key` of render_rays' result: compositing's
+    value for an all-zero raw wherever that does not depend on sample positions, else 0."""
+    if key in ("rgb_map", "rgb0"):
+        return 1.0 if white_bkgd else 0.0
+    if key in ("depth_map", "depth0"):
+        return float("nan")         # sum(w z) / sum(w) with sum(w) == 0 (composite_common.h)
+    return 0
+
+
+def _no_rays_result(device, N_samples, N_importance=0, retraw=False, predict_normals=False, early_stop=None,
+                    network_fn=None, network_fine=None, **_):
+    """render_rays' result for zero rays, without a field call (every ray of the frame missed)."""
+    f = dict(device=device, dtype=torch.float32)
+    M = N_samples + N_importance
+    fine = network_fn if network_fine is None else network_fine
+    ret = {}
+    for sfx, on in (("0", N_importance > 0), ("", True)):
+        if not on:
+            continue
+        names = ("rgb0", "depth0", "acc0", "sparsity_loss0") if sfx else ("rgb_map", "depth_map", "acc_map",
+                                                                          "sparsity_loss")
+        for k in names:
+            ret[k] = torch.empty((0, 3) if k.startswith("rgb") else (0,), **f)
+        if early_stop is not None:
+            ret["early_stop_samples" + sfx] = torch.empty(0, device=device, dtype=torch.int32)
+        if predict_normals:
+            net = network_fn if sfx else fine
+            ret["normal0" if sfx else "normal_map"] = torch.empty(0, 3 if getattr(net, "raw_channels", 4) == 7 else 0, **f)
+    if N_importance > 0:
+        ret["z_std"] = torch.empty(0, **f)
+    ret.update(pts=torch.empty(0, M, 3, **f), rays_d=torch.empty(0, 3, **f))
+    if retraw:
+        ret["raw"] = torch.empty(0, M, getattr(fine, "raw_channels", 4), **f)
+    return ret
+
+
+def _check_ray_bounds(grid):
+    from .occupancy import OccupancyGrid
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f"render: ray_bounds must be an OccupancyGrid, got {type(grid).__name__}")
+    if torch.is_grad_enabled():
+        raise ValueError("render: ray_bounds is forward-only (call under torch.no_grad(); rays are not bounded "
+                         "in training)")
+
+
+def _render_bounded(rays, chunk, grid, kwargs):
+    """batchify_rays over the rays that cross an occupied cell of `grid`, each with its own [near, far]
+    tightened to the span of those cells (csrc/ray_span.hip), scattered back to all rays."""
+    R = rays.shape[0]
+    hit, span, rows, rays_c = grid.bound_rays(rays)
+    if rows.shape[0] > 0:
+        part = batchify_rays(rays_c, chunk, **kwargs)
+    else:
+        part = _no_rays_result(rays.device, **kwargs)
+    if rows.shape[0] == R:          # every ray is hit, in order: nothing to scatter
+        all_ret = dict(part)
+    else:
+        white = bool(kwargs.get("white_bkgd", False))
+        idx = rows.long()
+        all_ret = {}
+        for k, v in part.items():
+            full = torch.full((R,) + tuple(v.shape[1:]), _missed_value(k, white), device=v.device, dtype=v.dtype)
+            all_ret[k] = full.index_copy_(0, idx, v)
+    all_ret.update(ray_hit=hit, ray_span=span)
+    return all_ret
+
+
 def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
-           c2w_staticcam=None, **kwargs):
-    """run_nerf.py:86-151 -> [rgb_map, depth_map, acc_map, extras]."""
+           c2w_staticcam=None, ray_bounds=None, **kwargs):
+    """run_nerf.py:86-151 -> [rgb_map, depth_map, acc_map, extras]. ray_bounds (an occupancy.OccupancyGrid;
+    forward-only rendering): the packed rays are marched through the grid first; a ray that
+    crosses no occupied cell gets the background without a field call, every other ray places its samples
+    between its first and its last occupied cell instead of over [near, far]. The extras then also hold
+    ray_hit (bool) and ray_span ([near', far'] per ray). Composes with occupancy= and early_stop=. None (the
+    default) leaves the call as it is without it."""
+    if ray_bounds is not None:
+        _check_ray_bounds(ray_bounds)
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, K, c2w)
     else:
@@ -638,7 +715,10 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
         rays = torch.cat([rays, torch.reshape(vd, [-1, 3]).float()], -1)
     else:
         rays = _pack_rays(H, W, K, rays_o, rays_d, near, far, ndc, use_viewdirs)
-    all_ret = batchify_rays(rays, chunk, **kwargs)
+    if ray_bounds is None:
+        all_ret = batchify_rays(rays, chunk, **kwargs)
+    else:
+        all_ret = _render_bounded(rays, chunk, ray_bounds, kwargs)
     for k in all_ret:
         all_ret[k] = torch.reshape(all_ret[k], list(sh[:-1]) + list(all_ret[k].shape[1:]))
     k_extract = ["rgb_map", "depth_map", "acc_map"]

@@ -17,8 +17,17 @@ threshold so small that nothing terminates (1e-300: the path's pure overhead —
 slab, one 4-byte read of the count per slab, no coarse-feature reuse). The dense frame of the unchanged
 path is the baseline.
 
+With --ray-bounds the same frame, process and method time per-ray sample bounds instead (render(ray_bounds=grid),
+csrc/ray_span.hip): through the grid of update()'s defaults, a grid with every cell set (the
+path's pure overhead: the span and gather launches and one 4-byte read per frame; every ray of this frame
+meets the box) and the scene's own geometry grid, each alone, on top of occupancy=, of early_stop= (1e-3, slabs
+of 32) and of both, next to occupancy= alone through the same grid; and, through the geometry grid, with half
+the samples (32 + 64) placed inside the spans. Per variant: the share of rays dropped, the mean span over
+far - near, the frame time and the PSNR.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
+       python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
 """
 import argparse
 import ast
@@ -183,6 +192,85 @@ def main_early_stop(a):
     print(json.dumps(out))
 
 
+def main_ray_bounds(a):
+    """The per-ray sample-bounds table: see the module docstring."""
+    bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
+    gpu = torch.device("cuda:0")
+    lo, hi = blender_bbox()
+    new_grid = lambda: nerf.OccupancyGrid(bbox, resolution=a.resolution, device=gpu)  # noqa: E731
+    grids = {"default grid": new_grid().update(emb, [coarse, fine]), "full grid": new_grid(),
+             "geometry grid": new_grid()}
+    grids["full grid"].set_mask(np.ones((a.resolution,) * 3, bool))
+    grids["geometry grid"].set_mask(geometry_mask(lo, hi, a.resolution))
+
+    H = W = a.size
+    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
+    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
+    pose = torch.from_numpy(pose_spherical(np.linspace(-180, 180, 101)[34], -30.0, 4.0311))[:3, :4].to(gpu)
+
+    def frame(over):
+        with torch.no_grad():
+            return nerf.render(H, W, K, chunk=a.chunk, c2w=pose, **dict(kw_test, **over))
+
+    def timed(over):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        frame(over)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    ro_np, rd_np = nerf.get_rays_np(H, W, K, pose.cpu().numpy())
+    target = torch.from_numpy(procedural_targets(np.ascontiguousarray(ro_np.reshape(-1, 3), np.float32),
+                                                 np.ascontiguousarray(rd_np.reshape(-1, 3), np.float32))).to(gpu)
+    psnr = lambda img: float(-10.0 * torch.log10(((img.reshape(-1, 3) - target) ** 2).mean()))  # noqa: E731
+
+    ert = dict(early_stop=1e-3, early_stop_slab=32)
+    variants = [("dense", {})]
+    for gname, grid in grids.items():
+        variants += [(f"{gname}: occupancy alone", dict(occupancy=grid)),
+                     (f"{gname}: ray_bounds", dict(ray_bounds=grid)),
+                     (f"{gname}: ray_bounds + occupancy", dict(ray_bounds=grid, occupancy=grid)),
+                     (f"{gname}: ray_bounds + early_stop", dict(ray_bounds=grid, **ert)),
+                     (f"{gname}: ray_bounds + occupancy + early_stop", dict(ray_bounds=grid, occupancy=grid, **ert))]
+    half = dict(N_samples=32, N_importance=64)
+    geo = grids["geometry grid"]
+    variants += [("32 + 64 samples, unbounded", half),
+                 ("geometry grid: ray_bounds, 32 + 64 samples", dict(ray_bounds=geo, **half)),
+                 ("geometry grid: ray_bounds + occupancy, 32 + 64 samples", dict(ray_bounds=geo, occupancy=geo, **half))]
+
+    report = {}
+    for name, over in variants:         # one untimed frame per variant: PSNR, rays dropped, span length
+        out = frame(over)
+        report[name] = {"psnr_db": psnr(out[0])}
+        if "ray_bounds" in over:
+            hit, span = out[3]["ray_hit"], out[3]["ray_span"]
+            length = (span[..., 1] - span[..., 0])[hit]
+            report[name].update(rays_dropped_share=1.0 - float(hit.float().mean()),
+                                span_over_far_minus_near=float(length.mean() / (kw_test["far"] - kw_test["near"]))
+                                if length.numel() else None)
+    for _, over in variants:            # warm-up of every variant
+        timed(over)
+    times = {name: [] for name, _ in variants}
+    for _ in range(a.frames):           # alternating
+        for name, over in variants:
+            times[name].append(timed(over))
+    for name, v in times.items():
+        report[name]["render_ms"] = {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)),
+                                     "frames": len(v)}
+        report[name]["speedup_vs_dense"] = float(np.median(times["dense"]) / np.median(v))
+    out = {"scene": f"two-sphere scene, {a.iters} training iterations", "frame": [H, W], "chunk": a.chunk,
+           "N_samples": 64, "N_importance": 128, "grid_resolution": a.resolution,
+           "grid_occupied_fraction": {k: g.occupied_fraction() for k, g in grids.items()},
+           "overhead_ms_full_grid_minus_dense": float(np.median(times["full grid: ray_bounds"]) -
+                                                      np.median(times["dense"])),
+           "variants": report, "device": torch.cuda.get_device_name(0)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fp:
+        json.dump(out, fp, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -192,11 +280,15 @@ def main():
     ap.add_argument("--resolution", type=int, default=128)
     ap.add_argument("--out", default=None)
     ap.add_argument("--early-stop", action="store_true", help="time early ray termination (DESIGN.md §14)")
+    ap.add_argument("--ray-bounds", action="store_true", help="time per-ray sample bounds (DESIGN.md §15)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = "profiles/early_stop_render_time.json" if a.early_stop else "bench_out/render_time.json"
+        a.out = ("profiles/early_stop_render_time.json" if a.early_stop else
+                 "profiles/ray_bounds_render_time.json" if a.ray_bounds else "bench_out/render_time.json")
     if a.early_stop:
         return main_early_stop(a)
+    if a.ray_bounds:
+        return main_ray_bounds(a)
     bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
     gpu = torch.device("cuda:0")
     lo, hi = blender_bbox()
