@@ -764,7 +764,8 @@ int nerf_priors_bwd(const float* d_depth, const float* d_normals, const float* d
 int nerf_nearest_pixel(const float* d_xy, int64_t n, const int64_t* d_idx1, int64_t n_query, int64_t* d_idx2,
                        float* d_dist, void* stream);
 
-/* ---- occupancy grid: empty-space skipping for forward-only rendering (csrc/occupancy.hip) -------
+/* ---- occupancy grid: empty-space skipping for forward-only rendering (csrc/occupancy.hip;
+ * nerf_occ_compact: csrc/sparse_points.hip) -------------------------------------------------------
  * Additive entries (the ABI version stays 12). The box is cut into res^3 cells (1 <= res <= 1024);
  * cell (ix, iy, iz) has id (ix*res + iy)*res + iz and owns bit (id & 31) of word id >> 5 of d_bits,
  * uint32[ceil(res^3 / 32)] (bits past res^3 are 0). Cell rule, per axis, in fp32 with
@@ -790,7 +791,9 @@ int nerf_nearest_pixel(const float* d_xy, int64_t n, const int64_t* d_idx1, int6
  *   sh_stride 16), for i < capacity <= n_points, and an all-zero row of d_raw [n_points, 4] for every
  *   skipped point; it reads the workspace a count stage over the same points and bits left. 3 = both
  *   in one call (capacity = n_points needs no host read); 1, a host read of the count, then 2 with
- *   capacity = count sizes the outputs to the kept points. */
+ *   capacity = count sizes the outputs to the kept points. It is nerf_ert_compact (below, the same
+ *   kernels) over the one slab [0, samples_per_ray) with every ray alive and d_bits required, except that
+ *   n_points need not be a multiple of samples_per_ray. */
 int nerf_occ_cell_points(const float* bbox_min, const float* bbox_max, int res, int64_t cell_begin, int64_t n_cells,
                          int n_per_cell, unsigned long long seed, unsigned long long offset, float* d_pts,
                          void* stream);
@@ -806,7 +809,8 @@ int nerf_occ_compact(const float* d_pts, int64_t n_points, const float* d_sh_ray
                      float* d_pts_c, float* d_sh_c, float* d_raw, void* d_workspace, size_t workspace_bytes,
                      void* stream);
 
-/* ---- early ray termination for forward-only rendering (csrc/early_stop.hip) ----------------------
+/* ---- early ray termination for forward-only rendering (csrc/early_stop.hip; nerf_ert_compact:
+ * csrc/sparse_points.hip) --------------------------------------------------------------------------
  * Additive entries (the ABI version stays 12). A field call over d_pts [n_rays, samples_per_ray, 3]
  * (point p = r * samples_per_ray + s) runs front to back in slabs [s0, s1) of samples.
  *
@@ -851,7 +855,8 @@ int nerf_ert_advance(const float* d_raw, const float* d_z, const float* d_rays_d
  *   workspace (nerf_ray_span_workspace_bytes(n_rays)) receives the counts per 4096 rays.
  * nerf_ray_span_gather: d_rows[i] (int32) = the i-th hit ray (ascending) and d_rays_c [capacity, n_cols]
  *   its row with columns 6 and 7 replaced by its span, for i < capacity <= n_rays; it reads d_hit, d_span
- *   and the workspace as nerf_ray_span over the same rays left them.
+ *   and the workspace as nerf_ray_span over the same rays left them (the block offsets and ranks of
+ *   csrc/compact_common.h, as the scatter stage of the two *_compact entries above).
  * n_rays = 0 (and, for the gather, capacity = 0) launches nothing and accepts NULL buffers. */
 size_t nerf_ray_span_workspace_bytes(int64_t n_rays);
 int nerf_ray_span(const float* d_rays, int64_t n_rays, int n_cols, const float* bbox_min, const float* bbox_max,

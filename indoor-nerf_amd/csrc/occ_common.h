@@ -1,5 +1,5 @@
 // The occupancy grid's cell rule (occupancy.hip has the layout and the rule in words), shared by the
-// grid's own kernels and the early-termination compaction (early_stop.hip).
+// grid's own kernels, the point compaction (sparse_points.hip) and the ray spans (ray_span.hip).
 #pragma once
 #include "field_common.h"
 

@@ -18,10 +18,8 @@
 // been <= 0 changes no composited value. For any other point it equals masking sigma there.
 //
 // Kernels: cell_points (sample positions of a range of cells), mark (OR any_k(sigma > thresh) into the
-// cells' bits), dilate (3x3x3 neighbourhood), query (per point: inside and bit set), compact (the
-// render path: the kept points of a field call in ascending order, with their positions and their
-// rays' SH4 rows gathered, and zero raw rows for the others; two launches, count / scatter, as
-// active.hip).
+// cells' bits), dilate (3x3x3 neighbourhood), query (per point: inside and bit set). The render path's
+// compaction of a field call's kept points (nerf_occ_compact) is sparse_points.hip.
 #include "occ_common.h"   // OccGrid, the cell rule, fill_grid
 
 namespace nerf {
@@ -107,103 +105,6 @@ __global__ void __launch_bounds__(256) occ_query_kernel(OccGrid g, const uint32_
     if (p < P) out[p] = occ_occupied(g, bits, pts + 3 * p) ? 1 : 0;
 }
 
-// ---------------------------------------------------------------- compaction (the render path)
-constexpr int kOccThreads = 256;
-constexpr int kOccPer = 16;                         // points per thread
-constexpr int kOccBlockPts = kOccThreads * kOccPer;  // 4096 points per block
-
-struct CompactArgs {
-    OccGrid g;
-    const uint32_t* bits;
-    const float* pts;        // [P, 3]
-    const float* sh_rays;    // [R, 40] per-ray SH records (nerf_sample_stratified_sh), or
-    const float* viewdirs;   // [R, 3]
-    int64_t P;
-    uint32_t rd_m; int rd_s; // p / samples_per_ray (udiv_magic)
-    int64_t capacity;        // rows of the compacted outputs
-    int32_t* rows;           // out [capacity]: kept points, ascending
-    int32_t* counts;         // out [1]
-    float* pts_c;            // out [capacity, 3]
-    float* sh_c;             // out [capacity, 16]
-    float* raw;              // [P, 4]: rows of skipped points are zeroed
-    int32_t* block_counts;   // workspace [n_blocks]
-};
-
-// point k of thread t of block b: b * kOccBlockPts + k * kOccThreads + t (consecutive threads, consecutive points)
-__global__ void __launch_bounds__(kOccThreads) occ_count_kernel(CompactArgs a) {
-    const int64_t base = (int64_t)blockIdx.x * kOccBlockPts;
-    int n = 0;
-#pragma unroll 4
-    for (int k = 0; k < kOccPer; ++k) {
-        const int64_t p = base + k * kOccThreads + threadIdx.x;
-        if (p < a.P && occ_occupied(a.g, a.bits, a.pts + 3 * p)) ++n;
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
-    __shared__ int s[kOccThreads / 64];
-    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = n;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int t = 0;
-        for (int i = 0; i < kOccThreads / 64; ++i) t += s[i];
-        a.block_counts[blockIdx.x] = t;
-        if (t) atomicAdd(a.counts, t);   // integer: the total does not depend on the order
-    }
-}
-
-__global__ void __launch_bounds__(kOccThreads) occ_scatter_kernel(CompactArgs a) {
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // this block's offset: the counts of the blocks before it
-    int off = 0;
-    for (int i = threadIdx.x; i < b; i += kOccThreads) off += a.block_counts[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
-    __shared__ int s_off[kOccThreads / 64];
-    __shared__ int s_cnt[kOccThreads / 64];
-    if (lane == 0) s_off[w] = off;
-    __syncthreads();
-    int64_t base = 0;
-    for (int i = 0; i < kOccThreads / 64; ++i) base += s_off[i];
-    __syncthreads();
-    const int64_t pbase = (int64_t)b * kOccBlockPts;
-    for (int k = 0; k < kOccPer; ++k) {
-        const int64_t p = pbase + k * kOccThreads + threadIdx.x;
-        float x = 0.f, y = 0.f, z = 0.f;
-        bool on = false;
-        if (p < a.P) {
-            x = a.pts[3 * p]; y = a.pts[3 * p + 1]; z = a.pts[3 * p + 2];
-            int id;
-            on = occ_cell(a.g, x, y, z, id) && occ_bit(a.bits, id);
-            if (!on) *reinterpret_cast<float4*>(a.raw + 4 * p) = make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-        const uint64_t m = __ballot(on);
-        const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-        if (lane == 0) s_cnt[w] = __popcll(m);
-        __syncthreads();
-        int64_t idx = base + __popcll(m & below);
-        for (int i = 0; i < w; ++i) idx += s_cnt[i];
-        if (on && idx < a.capacity) {
-            a.rows[idx] = (int32_t)p;
-            a.pts_c[3 * idx] = x; a.pts_c[3 * idx + 1] = y; a.pts_c[3 * idx + 2] = z;
-            const uint32_t ray = udiv_magic((uint32_t)p, a.rd_m, a.rd_s);
-            float4* dst = reinterpret_cast<float4*>(a.sh_c + 16 * idx);
-            if (a.sh_rays) {
-                const float4* src = reinterpret_cast<const float4*>(a.sh_rays + (int64_t)kShRecord * ray);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) dst[q] = src[q];
-            } else {
-                float o[16];
-                sh4_eval(a.viewdirs[3 * (int64_t)ray], a.viewdirs[3 * (int64_t)ray + 1], a.viewdirs[3 * (int64_t)ray + 2], o);
-#pragma unroll
-                for (int q = 0; q < 4; ++q) dst[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
-            }
-        }
-        for (int i = 0; i < kOccThreads / 64; ++i) base += s_cnt[i];
-        __syncthreads();
-    }
-}
-
 }  // namespace nerf
 
 using namespace nerf;
@@ -266,54 +167,5 @@ extern "C" int nerf_occ_query(const float* d_pts, int64_t n_points, const float*
     hipLaunchKernelGGL(occ_query_kernel, dim3(blocks_for(n_points, 256)), dim3(256), 0, as_stream(stream), g, d_bits,
                        d_pts, n_points, d_out);
     NERF_CHECK_LAUNCH("occ_query");
-    return NERF_OK;
-}
-
-extern "C" size_t nerf_occ_compact_workspace_bytes(int64_t n_points) {
-    if (n_points < 0) return 0;
-    return (size_t)std::max<int64_t>(1, (n_points + kOccBlockPts - 1) / kOccBlockPts) * sizeof(int32_t);
-}
-
-extern "C" int nerf_occ_compact(const float* d_pts, int64_t n_points, const float* d_sh_rays, const float* d_viewdirs,
-                                int64_t samples_per_ray, const float* bbox_min, const float* bbox_max, int res,
-                                const uint32_t* d_bits, int stages, int64_t capacity, int32_t* d_rows,
-                                int32_t* d_counts, float* d_pts_c, float* d_sh_c, float* d_raw, void* d_workspace,
-                                size_t workspace_bytes, void* stream) {
-    OccGrid g;
-    int rc = fill_grid(g, bbox_min, bbox_max, res);
-    if (rc) return rc;
-    NERF_REQUIRE(n_points >= 0 && n_points <= INT32_MAX, "occ_compact: n_points %lld", (long long)n_points);
-    NERF_REQUIRE(stages >= 1 && stages <= 3, "occ_compact: stages %d (1 count, 2 scatter, 3 both)", stages);
-    NERF_REQUIRE(d_counts && d_workspace && workspace_bytes >= nerf_occ_compact_workspace_bytes(n_points),
-                 "occ_compact: null counts / workspace, or workspace %zu B < %zu B", workspace_bytes,
-                 nerf_occ_compact_workspace_bytes(n_points));
-    NERF_REQUIRE(samples_per_ray >= 1, "occ_compact: samples_per_ray %lld", (long long)samples_per_ray);
-    NERF_REQUIRE(capacity >= 0 && capacity <= n_points, "occ_compact: capacity %lld of %lld points",
-                 (long long)capacity, (long long)n_points);
-    if (n_points > 0 && (stages & 2)) {
-        NERF_REQUIRE(d_raw && ((uintptr_t)d_raw & 15) == 0, "occ_compact: raw rows must be non-null and 16-B aligned");
-        NERF_REQUIRE((d_sh_rays != nullptr) != (d_viewdirs != nullptr),
-                     "occ_compact: exactly one of the per-ray SH records and the view directions");
-        NERF_REQUIRE(!d_sh_rays || ((uintptr_t)d_sh_rays & 15) == 0, "occ_compact: SH records must be 16-B aligned");
-        NERF_REQUIRE(capacity == 0 || (d_rows && d_pts_c && d_sh_c && ((uintptr_t)d_sh_c & 15) == 0),
-                     "occ_compact: null outputs, or sh_c not 16-B aligned");
-    }
-    NERF_REQUIRE(n_points == 0 || (d_pts && d_bits), "occ_compact: null arg");
-    if (stages & 1) {
-        if (hipMemsetAsync(d_counts, 0, sizeof(int32_t), as_stream(stream)) != hipSuccess) {
-            set_error("occ_compact: hipMemsetAsync failed");
-            return NERF_E_LAUNCH;
-        }
-    }
-    if (n_points == 0) return NERF_OK;
-    CompactArgs a{};
-    a.g = g; a.bits = d_bits; a.pts = d_pts; a.sh_rays = d_sh_rays; a.viewdirs = d_viewdirs; a.P = n_points;
-    ray_div_magic(samples_per_ray, a.rd_m, a.rd_s);
-    a.capacity = capacity; a.rows = d_rows; a.counts = d_counts; a.pts_c = d_pts_c; a.sh_c = d_sh_c; a.raw = d_raw;
-    a.block_counts = static_cast<int32_t*>(d_workspace);
-    const unsigned nb = blocks_for(n_points, kOccBlockPts);
-    if (stages & 1) hipLaunchKernelGGL(occ_count_kernel, dim3(nb), dim3(kOccThreads), 0, as_stream(stream), a);
-    if (stages & 2) hipLaunchKernelGGL(occ_scatter_kernel, dim3(nb), dim3(kOccThreads), 0, as_stream(stream), a);
-    NERF_CHECK_LAUNCH("occ_compact");
     return NERF_OK;
 }

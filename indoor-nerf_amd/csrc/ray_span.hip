@@ -3,8 +3,8 @@
 // For a packed ray row [o, d, near, far(, viewdir)] the span kernel walks the grid's cells along the ray
 // (a 3-D DDA after Amanatides & Woo) and reports whether the ray crosses an occupied cell inside
 // [near, far] and, if so, the span [near', far'] between the first and the last such cell, widened by
-// pad. The hit rows are then compacted (wave ballots + an LDS scan, as occupancy.hip) with columns 6 and 7
-// replaced by the span: render_rays runs on them unchanged.
+// pad. The hit rows are then compacted (compact_common.h's scheme, with the count side done per wave by the
+// span kernel itself) with columns 6 and 7 replaced by the span: render_rays runs on them unchanged.
 //
 // The rule (one thread per ray, fp32, every operation written out below; the file is built with
 // -ffp-contract=off and correctly rounded division, so it is the same bits as its NumPy fp32 restatement in
@@ -29,13 +29,12 @@
 // pad is a depth, and the position rounding it has to cover, divided by |d_a|, grows without bound as a
 // face is met at a shallower slope (DESIGN.md §15 has the slope down to which it holds). Past that limit a
 // sample within 2^-20 (|o_a| + |bound_a|) of an occupied cell's face may fall outside the span.
+#include "compact_common.h"
 #include "occ_common.h"
 
 namespace nerf {
 
-constexpr int kSpanThreads = 256;
-constexpr int kSpanPer = 16;                            // rays per thread of the compaction
-constexpr int kSpanBlockRays = kSpanThreads * kSpanPer;  // 4096 rays per compaction block
+constexpr int kSpanThreads = kCompactThreads;   // a span block is one iteration of a compaction block
 
 struct SpanArgs {
     OccGrid g;
@@ -148,7 +147,7 @@ __device__ __forceinline__ bool ray_span(const OccGrid& g, const uint32_t* __res
 }
 
 // one thread per ray (neighbouring threads are neighbouring pixels: a wave's walks are coherent); a wave adds
-// its hits to the count of its compaction block of kSpanBlockRays rays and to the total (integer adds: the
+// its hits to the count of its compaction block of kCompactBlock rays and to the total (integer adds: the
 // sums do not depend on the order)
 __global__ void __launch_bounds__(kSpanThreads) ray_span_kernel(SpanArgs a) {
     const int64_t r = (int64_t)blockIdx.x * kSpanThreads + threadIdx.x;
@@ -161,45 +160,24 @@ __global__ void __launch_bounds__(kSpanThreads) ray_span_kernel(SpanArgs a) {
     }
     const int n = __popcll(__ballot(h));
     if ((threadIdx.x & 63) == 0 && n) {
-        atomicAdd(a.block_counts + blockIdx.x / kSpanPer, n);
+        atomicAdd(a.block_counts + blockIdx.x / kCompactPer, n);
         atomicAdd(a.counts, n);
     }
 }
 
-__global__ void __launch_bounds__(kSpanThreads) ray_span_gather_kernel(SpanArgs a) {
-    const int b = blockIdx.x;
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    // this block's offset: the counts of the blocks before it
-    int off = 0;
-    for (int i = threadIdx.x; i < b; i += kSpanThreads) off += a.block_counts[i];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) off += __shfl_xor(off, o, 64);
-    __shared__ int s_off[kSpanThreads / 64];
-    __shared__ int s_cnt[kSpanThreads / 64];
-    if (lane == 0) s_off[w] = off;
-    __syncthreads();
-    int64_t base = 0;
-    for (int i = 0; i < kSpanThreads / 64; ++i) base += s_off[i];
-    __syncthreads();
-    const int64_t rbase = (int64_t)b * kSpanBlockRays;
-    for (int k = 0; k < kSpanPer; ++k) {
-        const int64_t r = rbase + k * kSpanThreads + threadIdx.x;
+__global__ void __launch_bounds__(kCompactThreads) ray_span_gather_kernel(SpanArgs a) {
+    int64_t base = compact_block_offset(a.block_counts);
+    for (int k = 0; k < kCompactPer; ++k) {
+        const int64_t r = compact_item(k);
         const bool on = r < a.R && a.hit[r] != 0;
-        const uint64_t m = __ballot(on);
-        const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-        if (lane == 0) s_cnt[w] = __popcll(m);
-        __syncthreads();
-        int64_t idx = base + __popcll(m & below);
-        for (int i = 0; i < w; ++i) idx += s_cnt[i];
-        if (on && idx < a.capacity) {
+        compact_place(on, base, [&](int64_t idx) {
+            if (idx >= a.capacity) return;
             a.rows[idx] = (int32_t)r;
             const float* src = a.rays + r * a.C;
             float* dst = a.rays_c + idx * a.C;
             for (int c = 0; c < a.C; ++c) dst[c] = src[c];
             dst[6] = a.span[2 * r]; dst[7] = a.span[2 * r + 1];
-        }
-        for (int i = 0; i < kSpanThreads / 64; ++i) base += s_cnt[i];
-        __syncthreads();
+        });
     }
 }
 
@@ -226,10 +204,7 @@ static int span_args(SpanArgs& a, const char* what, int64_t n_rays, int n_cols, 
 
 using namespace nerf;
 
-extern "C" size_t nerf_ray_span_workspace_bytes(int64_t n_rays) {
-    if (n_rays < 0) return 0;
-    return (size_t)std::max<int64_t>(1, (n_rays + kSpanBlockRays - 1) / kSpanBlockRays) * sizeof(int32_t);
-}
+extern "C" size_t nerf_ray_span_workspace_bytes(int64_t n_rays) { return compact_workspace_bytes(n_rays); }
 
 extern "C" int nerf_ray_span(const float* d_rays, int64_t n_rays, int n_cols, const float* bbox_min,
                              const float* bbox_max, int res, const uint32_t* d_bits, uint8_t* d_hit, float* d_span,
@@ -268,7 +243,7 @@ extern "C" int nerf_ray_span_gather(const float* d_rays, int64_t n_rays, int n_c
     a.rays = d_rays; a.R = n_rays; a.C = n_cols; a.hit = const_cast<uint8_t*>(d_hit);
     a.span = const_cast<float*>(d_span); a.capacity = capacity; a.rows = d_rows; a.rays_c = d_rays_c;
     a.block_counts = static_cast<int32_t*>(const_cast<void*>(d_workspace));
-    hipLaunchKernelGGL(ray_span_gather_kernel, dim3(blocks_for(n_rays, kSpanBlockRays)), dim3(kSpanThreads), 0,
+    hipLaunchKernelGGL(ray_span_gather_kernel, dim3(blocks_for(n_rays, kCompactBlock)), dim3(kCompactThreads), 0,
                        as_stream(stream), a);
     NERF_CHECK_LAUNCH("ray_span_gather");
     return NERF_OK;

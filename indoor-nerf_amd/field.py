@@ -647,16 +647,11 @@ def batchify(fn, chunk):
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):
     """run_nerf.py:53-68. inputs [..., S, 3], viewdirs [R, 3]. Fused when the modules are ours;
     netchunk is then only a memory knob the fused kernels do not need."""
-    ert = getattr(inputs, "_nerf_early_stop", None)   # early_stop.EarlyStopRequest of this render_rays call
-    if ert is not None:
-        from .early_stop import run_network_early_stop
-        ert.used = True
-        return run_network_early_stop(inputs, viewdirs, fn, embed_fn, embeddirs_fn, ert)
-    occ = getattr(inputs, "_nerf_occupancy", None)   # render._OccupancyRequest of this render_rays call
-    if occ is not None:
-        from .occupancy import run_network_occupancy
-        occ.used = True
-        return run_network_occupancy(inputs, viewdirs, fn, embed_fn, embeddirs_fn, occ.grid)
+    sparse = getattr(inputs, "_nerf_sparse", None)   # sparse_field.SparseRequest of this render_rays call
+    if sparse is not None:
+        from .sparse_field import run_network_sparse
+        sparse.used = True
+        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse)
     fused = (isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall)
              and isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3)
     if fused:

@@ -1,8 +1,8 @@
 """Occupancy grid of the scene box: empty-space skipping for forward-only rendering.
 
 A density bitfield over the scene box, built from the trained field (OccupancyGrid.update), and the
-field call render_rays makes with one (run_network_occupancy): the kept samples — inside the box and in
-an occupied cell — are compacted in ascending order (csrc/occupancy.hip), hash-encoded and run through
+field call render_rays makes with one (sparse_field.run_network_sparse): the kept samples — inside the box and in
+an occupied cell — are compacted in ascending order (csrc/sparse_points.hip), hash-encoded and run through
 the MLP, whose results land in their rows of raw; every skipped sample gets an all-zero raw row.
 Compositing gives a sample with relu(sigma) = 0 weight 0 exactly, so skipping a sample the dense path
 would have given relu(sigma) = 0 changes nothing, and skipping any other equals masking sigma there.
@@ -13,14 +13,14 @@ would have given relu(sigma) = 0 changes nothing, and skipping any other equals 
     render_kwargs_test["occupancy"] = grid                # render / render_path skip empty space
 
 Forward-only: no gradients, no raw noise, no normals head, no A-CAQ (render_rays and
-run_network_occupancy raise ValueError otherwise). The grid is not used in training and is not stored
+run_network_sparse raise ValueError otherwise). The grid is not used in training and is not stored
 in checkpoints.
 """
 import numpy as np
 import torch
 
 from . import _lib
-from .hashgrid import HashEmbedder, SHEncoder, _bbox_floats
+from .hashgrid import HashEmbedder, _bbox_floats
 
 MAX_RESOLUTION = 1024   # res^3 cell ids fit 32 bits (csrc/occupancy.hip)
 
@@ -204,39 +204,3 @@ class OccupancyGrid:
                       _lib.ptr(span, "span"), n, _lib.ptr(rows, "rows", torch.int32), _lib.ptr(rays_c, "rays_c"),
                       _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
         return hit, span, rows, rays_c
-
-
-def run_network_occupancy(inputs, viewdirs, fn, embed_fn, embeddirs_fn, grid):
-    """run_network (field.py) through an occupancy grid: inputs [R, S, 3], viewdirs [R, 3] ->
-    raw [R, S, 4] with the field evaluated at the kept samples only and zero rows elsewhere."""
-    from .field import _point_order, _weights_struct
-    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 3:
-        raise ValueError("occupancy: needs the fused field call (SHEncoder view encoding, viewdirs, inputs [R, S, 3])")
-    _check_modules(embed_fn, fn)
-    if fn.raw_channels != 4:
-        raise ValueError("occupancy: a normals head is not supported (run_network's box mask then lands on n_z, "
-                         "not on sigma, so a skipped sample is not a zero-weight sample)")
-    if torch.is_grad_enabled():
-        raise ValueError("occupancy: forward-only (call under torch.no_grad(); the grid is not used in training)")
-    if embed_fn.training:
-        embed_fn.current_step += 1
-    R, S = inputs.shape[0], inputs.shape[1]
-    P, dev = R * S, inputs.device
-    if 16 * (P + 32) >= 2 ** 31:
-        raise ValueError(f"occupancy: {P} points per field call exceed the MLP's 32-bit row indexing; use a smaller chunk")
-    pts = inputs.detach().reshape(-1, 3).float().contiguous()
-    sh_rays = getattr(viewdirs, "_nerf_sh", None)
-    viewdirs = viewdirs.detach().float().contiguous()
-    if sh_rays is not None:
-        viewdirs._nerf_sh = sh_rays
-    raw = torch.empty(P, 4, device=dev, dtype=torch.float32)
-    rows, pts_c, sh_c = grid.compact(pts, viewdirs, S, raw)
-    n = rows.shape[0]
-    if n > 0:
-        feat = torch.empty(embed_fn.n_levels, n, 2, device=dev, dtype=torch.float32)
-        keep = torch.empty(n, device=dev, dtype=torch.bool)
-        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep)
-        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * n, _lib.ptr(sh_c, "sh_c"), 16, None, 1,
-                  _lib.ptr(keep, "keep", torch.bool), n, _weights_struct(fn.mlp_weights()), _lib.ptr(raw, "raw"),
-                  None, None, None, 0, _point_order((rows, 0, 0)), _lib.stream())
-    return raw.reshape(R, S, 4)

@@ -374,33 +374,18 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return out
 
 
-class _OccupancyRequest:
-    """render_rays' occupancy grid on its way to the fused run_network (attached to the point tensor as
-    `pts._nerf_occupancy`); `used` tells render_rays that the query function took the occupancy path."""
-
-    def __init__(self, grid):
-        self.grid, self.used = grid, False
-
-
 def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None):
     """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
     (stops int32 [R], early_stop.py), None otherwise (stops None)."""
-    if early is not None:
-        from .early_stop import EarlyStopRequest
-        req = pts._nerf_early_stop = EarlyStopRequest(*early, grid=occupancy)
-        raw = network_query_fn(pts, viewdirs, fn)
-        del pts._nerf_early_stop
-        if not req.used:   # as below: never fall back to the dense path silently
-            raise ValueError("render_rays: early_stop needs a network_query_fn that calls this package's run_network")
-        return raw, req.stop
-    if occupancy is None:
+    if occupancy is None and early is None:
         return network_query_fn(pts, viewdirs, fn), None
-    req = pts._nerf_occupancy = _OccupancyRequest(occupancy)
+    from .sparse_field import SparseRequest
+    req = pts._nerf_sparse = SparseRequest(occupancy, early)
     raw = network_query_fn(pts, viewdirs, fn)
-    del pts._nerf_occupancy
+    del pts._nerf_sparse
     if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
-        raise ValueError("render_rays: occupancy needs a network_query_fn that calls this package's run_network")
-    return raw, None
+        raise ValueError(f"render_rays: {req.what} needs a network_query_fn that calls this package's run_network")
+    return raw, req.stop
 
 
 def last_early_stop_counts():
@@ -426,18 +411,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if early_stop is not None:
         from .early_stop import check_params
         early = check_params(early_stop, early_stop_slab)
+    if early is not None or occupancy is not None:
+        from .sparse_field import NOT_IN_TRAINING
+        what = "occupancy" if early is None else "early_stop"
         if torch.is_grad_enabled():
-            raise ValueError("render_rays: early_stop is forward-only (call under torch.no_grad(); rays are not "
-                             "stopped in training)")
+            raise ValueError(f"render_rays: {what} is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
         if raw_noise_std > 0.:
-            raise ValueError("render_rays: early_stop needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
-                             "at skipped samples)")
-    if occupancy is not None:
-        if torch.is_grad_enabled():
-            raise ValueError("render_rays: occupancy is forward-only (call under torch.no_grad(); the grid is not "
-                             "used in training)")
-        if raw_noise_std > 0.:
-            raise ValueError("render_rays: occupancy needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
+            raise ValueError(f"render_rays: {what} needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
                              "at skipped samples)")
     rays = ray_batch.detach().float().contiguous()
     R, C = rays.shape

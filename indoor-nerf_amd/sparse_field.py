@@ -1,0 +1,125 @@
+"""The field call of the forward-only render paths that evaluate only some samples: an occupancy grid
+(occupancy.py), early ray termination (early_stop.py), or both.
+
+render_rays attaches a SparseRequest to the point tensor of a pass; the fused run_network (field.py) hands
+the call to run_network_sparse. The kept samples are compacted in ascending order
+(csrc/sparse_points.hip), hash-encoded and run through the MLP, whose results land in their rows of raw;
+every other sample gets an all-zero raw row, which compositing gives weight 0 exactly.
+"""
+import torch
+
+from . import _lib
+from .early_stop import _LAST, tau_max_of
+from .hashgrid import SHEncoder
+from .occupancy import _check_modules
+
+# why each keyword is forward-only (render_rays' and run_network_sparse's refusals)
+NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training"}
+
+
+class SparseRequest:
+    """render_rays' request on its way to the fused run_network (attached to the point tensor as
+    `pts._nerf_sparse`): the occupancy grid or None, and early = (z [R, S], rays_d [R, 3], eps, slab) of
+    early ray termination or None. run_network sets `used` (a foreign query function leaves it False and
+    render_rays raises) and, with early, `stop` (int32 [R]: leading samples for which the ray was alive)."""
+
+    def __init__(self, grid=None, early=None):
+        self.grid, self.early = grid, early
+        self.used, self.stop = False, None
+
+    @property
+    def what(self):
+        """The keyword the request's messages name."""
+        return "occupancy" if self.early is None else "early_stop"
+
+
+def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+    """run_network (field.py) for a SparseRequest: inputs [R, S, 3], viewdirs [R, 3] -> raw [R, S, 4] with
+    the field evaluated at the kept samples only and zero rows elsewhere. Without early termination the call
+    is one slab through req.grid.compact; with it, slabs of req.early's size front to back, nerf_ert_advance
+    between them, and req.stop receives the stops."""
+    from .field import _point_order, _weights_struct
+    what = req.what
+    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 3:
+        raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, inputs [R, S, 3])")
+    _check_modules(embed_fn, fn, what)
+    if fn.raw_channels != 4:
+        raise ValueError(f"{what}: a normals head is not supported (run_network's box mask then lands on n_z, "
+                         "not on sigma, so a skipped sample is not a zero-weight sample)")
+    if torch.is_grad_enabled():
+        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+    if embed_fn.training:
+        embed_fn.current_step += 1
+    R, S = inputs.shape[0], inputs.shape[1]
+    P, dev, L = R * S, inputs.device, embed_fn.n_levels
+    if 16 * (P + 32) >= 2 ** 31:
+        raise ValueError(f"{what}: {P} points per field call exceed the MLP's 32-bit row indexing; use a smaller chunk")
+    if req.early is not None:
+        z, rays_d, eps, K = req.early
+        if tuple(z.shape) != (R, S) or tuple(rays_d.shape) != (R, 3):
+            raise ValueError("early_stop: z / rays_d of the request do not match the points")
+    pts = inputs.detach().reshape(-1, 3).float().contiguous()
+    sh_rays = getattr(viewdirs, "_nerf_sh", None)
+    viewdirs = viewdirs.detach().float().contiguous()
+    if sh_rays is not None:
+        viewdirs._nerf_sh = sh_rays
+    f, i32 = dict(device=dev, dtype=torch.float32), dict(device=dev, dtype=torch.int32)
+    raw = torch.empty(P, 4, **f)
+    weights = _weights_struct(fn.mlp_weights())
+
+    def field(n, rows, pts_c, sh_c, feat, keep):
+        """The field at the n compacted points; rows of raw `rows` receive the results."""
+        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep)
+        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * n, _lib.ptr(sh_c, "sh_c"), 16, None, 1,
+                  _lib.ptr(keep, "keep", torch.bool), n, weights, _lib.ptr(raw, "raw"),
+                  None, None, None, 0, _point_order((rows, 0, 0)), _lib.stream())
+
+    if req.early is None:
+        # one slab, no alive flags: the grid's own compaction, every buffer sized exactly after the count
+        rows, pts_c, sh_c = req.grid.compact(pts, viewdirs, S, raw)
+        n = rows.shape[0]
+        if n > 0:
+            field(n, rows, pts_c, sh_c, torch.empty(L, n, 2, **f), torch.empty(n, device=dev, dtype=torch.bool))
+        return raw.reshape(R, S, 4)
+
+    z, rays_d = z.detach().float().contiguous(), rays_d.detach().float().contiguous()
+    grid = req.grid
+    if grid is not None:
+        bmin, bmax, res, bits = grid._bmin, grid._bmax, grid.resolution, grid._bits()
+    else:
+        bmin, bmax, res, bits = embed_fn._meta["bmin"], embed_fn._meta["bmax"], 1, None   # the encoder's own box
+    tau_max = tau_max_of(eps)
+    tau = torch.zeros(R, **f)
+    alive = torch.ones(R, device=dev, dtype=torch.uint8)
+    stop = torch.full((R,), S, **i32)
+    # scratch of the worst-case slab (every candidate kept), once per field call
+    cap = R * min(K, S)
+    count = torch.empty(1, **i32)
+    ws = torch.empty(int(_lib.load().nerf_ert_compact_workspace_bytes(cap)) // 4, **i32)
+    rows, pts_c, sh_c = torch.empty(cap, **i32), torch.empty(cap, 3, **f), torch.empty(cap, 16, **f)
+    feat, keep = torch.empty(L * cap * 2, **f), torch.empty(cap, device=dev, dtype=torch.bool)
+    evaluated = 0
+
+    def compact(s0, s1, stages, n):
+        _lib.call("nerf_ert_compact", _lib.ptr(pts, "pts"), R, S, s0, s1, _lib.ptr(alive, "alive", torch.uint8),
+                  _lib.ptr(sh_rays, "sh_rows", allow_none=True),
+                  None if sh_rays is not None else _lib.ptr(viewdirs, "viewdirs"), bmin, bmax, res, bits, stages, n,
+                  _lib.ptr(rows, "rows", torch.int32), _lib.ptr(count, "count", torch.int32),
+                  _lib.ptr(pts_c, "pts_c"), _lib.ptr(sh_c, "sh_c"), _lib.ptr(raw, "raw"),
+                  _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+
+    for s0 in range(0, S if R > 0 else 0, K):
+        s1 = min(s0 + K, S)
+        compact(s0, s1, 1, 0)
+        n = int(count.item())      # one 4-byte host read per slab sizes the encode and MLP launches
+        compact(s0, s1, 2, n)
+        if n > 0:
+            field(n, rows, pts_c[:n], sh_c, feat[:L * n * 2], keep[:n])
+        evaluated += n
+        if s1 < S:
+            _lib.call("nerf_ert_advance", _lib.ptr(raw, "raw"), _lib.ptr(z, "z"), _lib.ptr(rays_d, "rays_d"), R, S,
+                      s0, s1, tau_max, _lib.ptr(tau, "tau"), _lib.ptr(alive, "alive", torch.uint8),
+                      _lib.ptr(stop, "stop", torch.int32), _lib.stream())
+    _LAST["counts"] = (evaluated, P)
+    req.stop = stop
+    return raw.reshape(R, S, 4)
