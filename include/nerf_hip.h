@@ -866,6 +866,42 @@ int nerf_ray_span_gather(const float* d_rays, int64_t n_rays, int n_cols, const 
                          int64_t capacity, int32_t* d_rows, float* d_rays_c, const void* d_workspace,
                          size_t workspace_bytes, void* stream);
 
+/* ---- grid ray marching for forward-only rendering (csrc/march.hip) ----------------------------------
+ * Additive entries (the ABI version stays 12). d_rays [n_rays, n_cols] are packed ray rows as above, the
+ * box, res and d_bits an occupancy grid as above, d_t [n_samples] the sampler's table (linspace(0, 1,
+ * n_samples)), 1 <= n_samples <= 4096 and n_rays * n_samples <= 2^31 - 1. Lattice sample k of a ray, in
+ * fp32 without contraction: z_k = near * (1 - t_k) + far * t_k, p_k = o + d * z_k, dist_k = z_{k+1} - z_k
+ * (1e10 for the last). It is kept when nerf_occ_query(p_k) is 1. The kept samples of ray r, ascending in k,
+ * are entries [d_offsets[r], d_offsets[r + 1]) of the packed list; rays ascending.
+ *
+ * nerf_march_count: d_counts[r] (int32) = kept samples of ray r, d_offsets [n_rays + 1] (int32) their
+ *   exclusive scan (d_offsets[n_rays] = the list's length; one host read of it sizes the list),
+ *   d_rays_d [n_rays, 3] (optional) the rays' directions, contiguous. The workspace
+ *   (nerf_march_workspace_bytes(n_rays)) receives the counts per 4096 rays.
+ * nerf_march_write: the list, from d_counts and d_offsets as nerf_march_count over the same rays, table and
+ *   bits left them; n_points = the list's length as the host read it, capacity >= n_points the rows of the
+ *   outputs: d_pts_c [capacity, 3] = p_k, d_z_c [capacity] = z_k, d_dist_c [capacity] = dist_k and
+ *   d_sh_c [capacity, 16] (optional; n_cols = 11, 16-B aligned) = the fp32 SH4 coefficients of the ray's view
+ *   direction (the nerf_mlp_* entries' d_sh at sh_stride 16).
+ * nerf_march_composite: forward compositing (nerf_composite_fwd's per-sample arithmetic and fp64 scans) of
+ *   the packed d_raw [n_points, 4], d_z [n_points], d_dist [n_points] with d_rays_d [n_rays, 3]: d_rgb
+ *   [n_rays, 3] (+ 1 - acc with white_bkgd), d_disp (optional), d_acc, d_depth [n_rays] and d_weights
+ *   [n_points] (optional). A ray with an empty segment gets rgb 0 (1 with white_bkgd), acc 0, depth NaN. Any
+ *   segment length works; no entropy, normals or noise.
+ * n_rays = 0 (and, for the write, n_points = 0) launches nothing and accepts NULL buffers. */
+size_t nerf_march_workspace_bytes(int64_t n_rays);
+int nerf_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                     const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                     int32_t* d_counts, int32_t* d_offsets, float* d_rays_d, void* d_workspace,
+                     size_t workspace_bytes, void* stream);
+int nerf_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                     const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                     const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points, int64_t capacity,
+                     float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream);
+int nerf_march_composite(const float* d_raw, const float* d_z, const float* d_dist, const int32_t* d_offsets,
+                         const float* d_rays_d, int64_t n_rays, int64_t n_points, int white_bkgd, float* d_rgb,
+                         float* d_disp, float* d_acc, float* d_depth, float* d_weights, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

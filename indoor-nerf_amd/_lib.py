@@ -248,6 +248,11 @@ SIGNATURES = {
     "nerf_ert_advance": [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_i64, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
     "nerf_ray_span": [c_vp, c_i64, c_int, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
     "nerf_ray_span_gather": [c_vp, c_i64, c_int, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "nerf_march_count": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                         ctypes.c_size_t, c_vp],
+    "nerf_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_i64, c_i64,
+                         c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nerf_march_composite": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
 }
 
 _lib = None
@@ -291,6 +296,9 @@ def load():
     if hasattr(lib, "nerf_ray_span_workspace_bytes"):      # additive, as above
         lib.nerf_ray_span_workspace_bytes.restype = ctypes.c_size_t
         lib.nerf_ray_span_workspace_bytes.argtypes = [c_i64]
+    if hasattr(lib, "nerf_march_workspace_bytes"):         # additive, as above
+        lib.nerf_march_workspace_bytes.restype = ctypes.c_size_t
+        lib.nerf_march_workspace_bytes.argtypes = [c_i64]
     if hasattr(lib, "nerf_mlp_h3_bytes"):   # ABI 10 (an older A/B variant may lack it)
         lib.nerf_mlp_h3_bytes.restype = ctypes.c_size_t
         lib.nerf_mlp_h3_bytes.argtypes = [c_i64]
@@ -314,7 +322,8 @@ def exported_symbols():
             "nerf_quant_packed_bytes", "nerf_mlp_bwd_det_workspace_bytes", "nerf_priors_workspace_bytes",
             "nerf_normal_head_bwd_workspace_bytes", "nerf_active_rows_workspace_bytes",
             "nerf_mlp_h3_bytes", "nerf_occ_compact_workspace_bytes",
-            "nerf_ert_compact_workspace_bytes", "nerf_ray_span_workspace_bytes"] + list(SIGNATURES)
+            "nerf_ert_compact_workspace_bytes", "nerf_ray_span_workspace_bytes",
+            "nerf_march_workspace_bytes"] + list(SIGNATURES)
 
 
 _TIMING = None   # when a list: (name, start_event, end_event) per launch, recorded on the current stream

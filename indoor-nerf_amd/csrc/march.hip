@@ -1,0 +1,328 @@
+// Grid ray marching for forward-only rendering: a ray's samples in occupied cells as a packed
+// variable-length list, and the compositing of such a list. The dense [R, K] arrays are never formed.
+//
+// The lattice of a packed ray row [o, d, near, far(, viewdir)] with the sampler's table t [K] (every operation
+// fp32 and written out; the file is built with -ffp-contract=off, so these are the bits of sampling.hip's
+// unperturbed coarse samples with lindisp = 0):
+//   z_k = near * (1.0f - t_k) + far * t_k;   p_k = o + d * z_k per axis;
+//   dist_k = z_{k+1} - z_k for k < K - 1, 1e10f for k = K - 1: the distance to the next LATTICE sample, kept
+//   or not, which is what compositing computes from the dense z.
+// Sample k of ray r is kept when p_k is inside the box and its cell's bit is set (occ_common.h's cell rule, the
+// answer of nerf_occ_query). The kept samples of ray r, in ascending k, are entries [off[r], off[r + 1]) of
+// the list, rays ascending: the list is the dense array's kept entries in row-major order.
+//
+// One wave per ray, lane l of iteration i tests lattice index 64 i + l; a ballot counts the kept lanes.
+//   nerf_march_count: counts [R] (one store per ray) and, per block of kCompactBlock rays, the sum of its counts
+//     (integer atomic adds: the sums do not depend on the order the waves run in); then off [R + 1], the
+//     exclusive scan of counts, by compact_common.h's block offsets and a scan inside each block.
+//   nerf_march_write: the same walk; a kept sample's rank is off[r] + the kept samples of the ray's earlier
+//     iterations + the kept lanes below its own. Writes pts_c, z_c, dist_c and the ray's SH4 row per point.
+//   nerf_march_composite: packed forward compositing, one wave per ray, 64 entries per iteration. The
+//     per-sample arithmetic is composite_common.h's ray_forward restated (that header is on the training path
+//     and is not touched from here): sigmoid, relu, expf(-relu_s * dist * |d|), alpha = 1 - e,
+//     t = (1 - alpha) + 1e-10f, w = alpha * (float)T with T the fp64 exclusive product of t over the ray's
+//     earlier entries (a wave scan times a running carry); the ray sums are per-lane fp64 accumulators,
+//     reduced once. A skipped sample has alpha = 0 and t = 1.0f exactly, so leaving it out changes no
+//     product and no sum as a real number; only the fp64 association differs from the dense kernel.
+#include "compact_common.h"
+#include "occ_common.h"
+
+namespace nerf {
+
+constexpr int kMarchThreads = 256;
+constexpr int kMarchWaves = kMarchThreads / 64;   // rays per block
+constexpr int kMarchMaxSamples = 4096;
+
+struct MarchArgs {
+    OccGrid g;
+    const uint32_t* bits;
+    const float* rays;       // [R, C]
+    int64_t R;
+    int C, K;
+    const float* t;          // [K]
+    int32_t* counts;         // [R]
+    int32_t* off;            // [R + 1]
+    float* rays_d;           // optional out [R, 3]
+    int32_t* block_counts;   // workspace [ceil(R / kCompactBlock)]
+    int64_t capacity;        // rows of the packed outputs
+    float* pts_c;            // out [capacity, 3]
+    float* z_c;              // out [capacity]
+    float* dist_c;           // out [capacity]
+    float* sh_c;             // optional out [capacity, 16] (C == 11)
+};
+
+struct MarchRay {
+    float o[3], d[3], near, far;
+};
+
+__device__ __forceinline__ MarchRay march_ray(const MarchArgs& a, int64_t r) {
+    const float* ray = a.rays + r * a.C;
+    MarchRay m;
+    m.o[0] = ray[0]; m.o[1] = ray[1]; m.o[2] = ray[2];
+    m.d[0] = ray[3]; m.d[1] = ray[4]; m.d[2] = ray[5];
+    m.near = ray[6]; m.far = ray[7];
+    return m;
+}
+
+// sampling.hip's base_depth with lindisp = 0
+__device__ __forceinline__ float march_depth(const MarchRay& m, float t) { return m.near * (1.0f - t) + m.far * t; }
+
+// lattice sample k < K of the ray: its depth, its position and whether it is kept
+__device__ __forceinline__ bool march_sample(const MarchArgs& a, const MarchRay& m, int k, float& z, float* p) {
+    z = march_depth(m, a.t[k]);
+    p[0] = m.o[0] + m.d[0] * z;
+    p[1] = m.o[1] + m.d[1] * z;
+    p[2] = m.o[2] + m.d[2] * z;
+    return occ_occupied(a.g, a.bits, p);
+}
+
+__global__ void __launch_bounds__(kMarchThreads) march_count_kernel(MarchArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
+    if (r >= a.R) return;   // wave-uniform
+    const MarchRay m = march_ray(a, r);
+    int n = 0;
+    for (int k0 = 0; k0 < a.K; k0 += 64) {
+        const int k = k0 + lane;
+        bool on = false;
+        if (k < a.K) {
+            float z, p[3];
+            on = march_sample(a, m, k, z, p);
+        }
+        n += __popcll(__ballot(on));
+    }
+    if (lane == 0) {
+        a.counts[r] = n;
+        if (n) atomicAdd(a.block_counts + r / kCompactBlock, n);
+        if (a.rays_d) {
+            a.rays_d[3 * r] = m.d[0]; a.rays_d[3 * r + 1] = m.d[1]; a.rays_d[3 * r + 2] = m.d[2];
+        }
+    }
+}
+
+// off = exclusive scan of counts: item = ray, block offsets from compact_common.h, an inclusive wave scan and
+// the waves' totals inside each iteration of 256 rays
+__global__ void __launch_bounds__(kCompactThreads) march_offsets_kernel(MarchArgs a) {
+    int64_t base = compact_block_offset(a.block_counts);
+    __shared__ int s_w[kCompactWaves];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int k = 0; k < kCompactPer; ++k) {
+        const int64_t r = compact_item(k);
+        const int c = r < a.R ? a.counts[r] : 0;
+        int incl = c;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int v = __shfl_up(incl, o, 64);
+            if (lane >= o) incl += v;
+        }
+        if (lane == 63) s_w[w] = incl;
+        __syncthreads();
+        int64_t off = base + (incl - c);
+        for (int i = 0; i < w; ++i) off += s_w[i];
+        if (r < a.R) {
+            a.off[r] = (int32_t)off;
+            if (r == a.R - 1) a.off[a.R] = (int32_t)(off + c);
+        }
+        for (int i = 0; i < kCompactWaves; ++i) base += s_w[i];
+        __syncthreads();
+    }
+}
+
+__global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
+    if (r >= a.R) return;   // wave-uniform
+    if (a.counts[r] == 0) return;
+    const MarchRay m = march_ray(a, r);
+    float sh[16] = {};
+    if (a.sh_c) {
+        const float* v = a.rays + r * a.C + 8;
+        sh4_eval(v[0], v[1], v[2], sh);
+    }
+    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int64_t base = a.off[r];
+    for (int k0 = 0; k0 < a.K; k0 += 64) {
+        const int k = k0 + lane;
+        bool on = false;
+        float z = 0.f, p[3] = {0.f, 0.f, 0.f};
+        if (k < a.K) on = march_sample(a, m, k, z, p);
+        const uint64_t mask = __ballot(on);
+        const int64_t idx = base + __popcll(mask & below);
+        if (on && idx >= 0 && idx < a.capacity) {
+            a.pts_c[3 * idx] = p[0]; a.pts_c[3 * idx + 1] = p[1]; a.pts_c[3 * idx + 2] = p[2];
+            a.z_c[idx] = z;
+            a.dist_c[idx] = k + 1 < a.K ? march_depth(m, a.t[k + 1]) - z : 1e10f;
+            if (a.sh_c) {
+                float4* dst = reinterpret_cast<float4*>(a.sh_c + 16 * idx);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) dst[q] = make_float4(sh[4 * q], sh[4 * q + 1], sh[4 * q + 2], sh[4 * q + 3]);
+            }
+        }
+        base += __popcll(mask);
+    }
+}
+
+// ---------------------------------------------------------------- packed compositing
+struct MarchCompositeArgs {
+    const float* raw;        // [n, 4]
+    const float* z;          // [n]
+    const float* dist;       // [n]
+    const int32_t* off;      // [R + 1]
+    const float* rays_d;     // [R, 3]
+    int64_t R, n;
+    int white;
+    float* rgb; float* disp; float* acc; float* depth;   // [R, 3], [R], [R], [R]
+    float* weights;          // optional [n]
+};
+
+// composite_common.h's sigmoidf
+__device__ __forceinline__ float march_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
+
+__global__ void __launch_bounds__(kMarchThreads) march_composite_kernel(MarchCompositeArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
+    if (r >= a.R) return;   // wave-uniform: every lane of a live wave takes part in the scans below
+    const float dx = a.rays_d[3 * r], dy = a.rays_d[3 * r + 1], dz = a.rays_d[3 * r + 2];
+    const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
+    // the segment, held inside the list whatever the offsets say
+    int64_t end = a.off[r + 1], beg = a.off[r];
+    end = end < 0 ? 0 : (end > a.n ? a.n : end);
+    beg = beg < 0 ? 0 : (beg > end ? end : beg);
+    double carry = 1.0, r0 = 0, r1 = 0, r2 = 0, acc = 0, dn = 0;
+    for (int64_t j0 = beg; j0 < end; j0 += 64) {
+        const int64_t j = j0 + lane;
+        float c0 = 0.f, c1 = 0.f, c2 = 0.f, zj = 0.f, alpha = 0.f, t = 1.f;
+        if (j < end) {
+            const float4 rw = *reinterpret_cast<const float4*>(a.raw + 4 * j);
+            zj = a.z[j];
+            const float delta = a.dist[j] * norm_d;
+            c0 = march_sigmoid(rw.x); c1 = march_sigmoid(rw.y); c2 = march_sigmoid(rw.z);
+            const float sg = rw.w;
+            const float relu_s = sg > 0.f ? sg : 0.f;
+            const float e = expf(-relu_s * delta);
+            alpha = 1.0f - e;
+            t = (1.0f - alpha) + 1e-10f;
+        }
+        const double excl = wave_excl_prod_dpp((double)t);
+        const double T = carry * excl;
+        const float w = alpha * (float)T;
+        carry = carry * readlane_d(excl * (double)t, 63);
+        r0 += (double)(w * c0);
+        r1 += (double)(w * c1);
+        r2 += (double)(w * c2);
+        acc += (double)w;
+        dn += (double)(w * zj);
+        if (a.weights && j < end) a.weights[j] = w;
+    }
+    float rgb0 = (float)wave_sum_dpp(r0), rgb1 = (float)wave_sum_dpp(r1), rgb2 = (float)wave_sum_dpp(r2);
+    const float facc = (float)wave_sum_dpp(acc);
+    const float num = (float)wave_sum_dpp(dn);
+    if (lane == 0) {
+        const float depth = num / facc;   // NaN at 0 / 0, as ray_sums
+        const float mx = (depth != depth) ? depth : fmaxf(1e-10f, depth);
+        if (a.white) {
+            const float bg = 1.0f - facc;
+            rgb0 = rgb0 + bg; rgb1 = rgb1 + bg; rgb2 = rgb2 + bg;
+        }
+        a.rgb[3 * r] = rgb0; a.rgb[3 * r + 1] = rgb1; a.rgb[3 * r + 2] = rgb2;
+        a.acc[r] = facc;
+        a.depth[r] = depth;
+        if (a.disp) a.disp[r] = 1.0f / mx;
+    }
+}
+
+// the checks the count and the write entries share
+static int march_args(MarchArgs& a, const char* what, int64_t n_rays, int n_cols, int64_t n_samples,
+                      const float* bmin, const float* bmax, int res, bool needs_ws, void* d_workspace,
+                      size_t workspace_bytes) {
+    int rc = fill_grid(a.g, bmin, bmax, res);
+    if (rc) return rc;
+    NERF_REQUIRE(n_rays >= 0 && n_rays <= INT32_MAX, "%s: n_rays %lld", what, (long long)n_rays);
+    NERF_REQUIRE(n_cols == 8 || n_cols == 11, "%s: ray rows of %d columns (8 or 11)", what, n_cols);
+    NERF_REQUIRE(n_samples >= 1 && n_samples <= kMarchMaxSamples, "%s: n_samples %lld (1..%d)", what,
+                 (long long)n_samples, kMarchMaxSamples);
+    NERF_REQUIRE(n_rays * n_samples <= INT32_MAX, "%s: %lld rays x %lld samples exceed 2^31 - 1; use a smaller chunk",
+                 what, (long long)n_rays, (long long)n_samples);
+    const size_t need = compact_workspace_bytes(n_rays);
+    NERF_REQUIRE(!needs_ws || n_rays == 0 || (d_workspace && workspace_bytes >= need),
+                 "%s: null workspace, or workspace %zu B < %zu B", what, workspace_bytes, need);
+    a.R = n_rays; a.C = n_cols; a.K = (int)n_samples;
+    a.block_counts = needs_ws ? static_cast<int32_t*>(d_workspace) : nullptr;
+    return NERF_OK;
+}
+
+}  // namespace nerf
+
+using namespace nerf;
+
+extern "C" size_t nerf_march_workspace_bytes(int64_t n_rays) { return compact_workspace_bytes(n_rays); }
+
+extern "C" int nerf_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                                const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                                int32_t* d_counts, int32_t* d_offsets, float* d_rays_d, void* d_workspace,
+                                size_t workspace_bytes, void* stream) {
+    MarchArgs a{};
+    int rc = march_args(a, "march_count", n_rays, n_cols, n_samples, bbox_min, bbox_max, res, true, d_workspace,
+                        workspace_bytes);
+    if (rc) return rc;
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets, "march_count: null arg");
+    if (hipMemsetAsync(d_workspace, 0, compact_workspace_bytes(n_rays), as_stream(stream)) != hipSuccess) {
+        set_error("march_count: hipMemsetAsync failed");
+        return NERF_E_LAUNCH;
+    }
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = d_counts; a.off = d_offsets; a.rays_d = d_rays_d;
+    hipLaunchKernelGGL(march_count_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+                       as_stream(stream), a);
+    hipLaunchKernelGGL(march_offsets_kernel, dim3(blocks_for(n_rays, kCompactBlock)), dim3(kCompactThreads), 0,
+                       as_stream(stream), a);
+    NERF_CHECK_LAUNCH("march_count");
+    return NERF_OK;
+}
+
+extern "C" int nerf_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                                const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                                const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points, int64_t capacity,
+                                float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
+    MarchArgs a{};
+    int rc = march_args(a, "march_write", n_rays, n_cols, n_samples, bbox_min, bbox_max, res, false, nullptr, 0);
+    if (rc) return rc;
+    NERF_REQUIRE(n_points >= 0 && n_points <= n_rays * n_samples, "march_write: count %lld of %lld lattice samples",
+                 (long long)n_points, (long long)(n_rays * n_samples));
+    NERF_REQUIRE(capacity >= n_points, "march_write: capacity %lld below the count %lld", (long long)capacity,
+                 (long long)n_points);
+    if (n_rays == 0 || n_points == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets && d_pts_c && d_z_c && d_dist_c,
+                 "march_write: null arg");
+    NERF_REQUIRE(!d_sh_c || (n_cols == 11 && ((uintptr_t)d_sh_c & 15) == 0),
+                 "march_write: SH rows need ray rows of 11 columns and a 16-B aligned sh_c");
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = const_cast<int32_t*>(d_counts);
+    a.off = const_cast<int32_t*>(d_offsets);
+    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c;
+    hipLaunchKernelGGL(march_write_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+                       as_stream(stream), a);
+    NERF_CHECK_LAUNCH("march_write");
+    return NERF_OK;
+}
+
+extern "C" int nerf_march_composite(const float* d_raw, const float* d_z, const float* d_dist,
+                                    const int32_t* d_offsets, const float* d_rays_d, int64_t n_rays, int64_t n_points,
+                                    int white_bkgd, float* d_rgb, float* d_disp, float* d_acc, float* d_depth,
+                                    float* d_weights, void* stream) {
+    NERF_REQUIRE(n_rays >= 0 && n_rays <= INT32_MAX, "march_composite: n_rays %lld", (long long)n_rays);
+    NERF_REQUIRE(n_points >= 0 && n_points <= INT32_MAX && n_points <= n_rays * kMarchMaxSamples,
+                 "march_composite: n_points %lld of %lld rays (at most %d each)", (long long)n_points,
+                 (long long)n_rays, kMarchMaxSamples);
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_offsets && d_rays_d && d_rgb && d_acc && d_depth, "march_composite: null arg");
+    NERF_REQUIRE(n_points == 0 || (d_raw && d_z && d_dist && ((uintptr_t)d_raw & 15) == 0),
+                 "march_composite: null arg, or raw rows not 16-B aligned");
+    MarchCompositeArgs a{};
+    a.raw = d_raw; a.z = d_z; a.dist = d_dist; a.off = d_offsets; a.rays_d = d_rays_d; a.R = n_rays; a.n = n_points;
+    a.white = white_bkgd ? 1 : 0; a.rgb = d_rgb; a.disp = d_disp; a.acc = d_acc; a.depth = d_depth;
+    a.weights = d_weights;
+    hipLaunchKernelGGL(march_composite_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+                       as_stream(stream), a);
+    NERF_CHECK_LAUNCH("march_composite");
+    return NERF_OK;
+}

@@ -36,6 +36,15 @@ def _check_modules(embed_fn, fn, what="occupancy"):
                          "activation calibration depends on which points come first)")
 
 
+MAX_MARCH_SAMPLES = 4096   # lattice samples per ray of a march (csrc/march.hip)
+
+
+def check_march_samples(K, what):
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or not 1 <= K <= MAX_MARCH_SAMPLES:
+        raise ValueError(f"{what}: march_samples must be an integer in 1..{MAX_MARCH_SAMPLES}, got {K!r}")
+    return int(K)
+
+
 class OccupancyGrid:
     """Density bitfield over `bounding_box`: resolution^3 cells, cell (ix, iy, iz) = bit
     (ix*res + iy)*res + iz (csrc/occupancy.hip has the cell rule). A new grid is empty."""
@@ -204,3 +213,53 @@ class OccupancyGrid:
                       _lib.ptr(span, "span"), n, _lib.ptr(rows, "rows", torch.int32), _lib.ptr(rays_c, "rays_c"),
                       _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
         return hit, span, rows, rays_c
+
+    # ---- grid ray marching (csrc/march.hip) ----------------------------------------
+    def _march_count(self, rays, K):
+        """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n)."""
+        from .render import _linspace
+        if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] not in (8, 11):
+            raise ValueError("OccupancyGrid.march: rays must be packed rows [R, 8] or [R, 11] (o, d, near, far"
+                             f"[, viewdir]), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}")
+        K = check_march_samples(K, "OccupancyGrid.march")
+        rays = rays.detach().float().contiguous()
+        R, C, dev = rays.shape[0], rays.shape[1], rays.device
+        if R * K > 2 ** 31 - 1:
+            raise ValueError(f"OccupancyGrid.march: {R} rays x {K} samples exceed 2^31 - 1; use a smaller chunk")
+        i32 = dict(device=dev, dtype=torch.int32)
+        t = _linspace(K, dev)
+        counts, offsets = torch.empty(R, **i32), torch.zeros(R + 1, **i32) if R == 0 else torch.empty(R + 1, **i32)
+        rays_d = torch.empty(R, 3, device=dev, dtype=torch.float32)
+        n = 0
+        if R > 0:
+            ws = torch.empty(int(_lib.load().nerf_march_workspace_bytes(R)) // 4, **i32)
+            _lib.call("nerf_march_count", _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, self._bmin, self._bmax,
+                      self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
+                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"),
+                      _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+            n = int(offsets[R].item())     # one 4-byte host read sizes the list
+        return rays, t, counts, offsets, rays_d, n
+
+    def _march_write(self, rays, t, K, counts, offsets, n, sh):
+        R, C, dev = rays.shape[0], rays.shape[1], rays.device
+        f = dict(device=dev, dtype=torch.float32)
+        pts_c, z_c, dist_c = torch.empty(n, 3, **f), torch.empty(n, **f), torch.empty(n, **f)
+        sh_c = torch.empty(n, 16, **f) if sh else None
+        if n > 0:
+            _lib.call("nerf_march_write", _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, self._bmin, self._bmax,
+                      self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
+                      _lib.ptr(offsets, "offsets", torch.int32), n, n, _lib.ptr(pts_c, "pts_c"), _lib.ptr(z_c, "z_c"),
+                      _lib.ptr(dist_c, "dist_c"), _lib.ptr(sh_c, "sh_c", allow_none=True), _lib.stream())
+        return pts_c, z_c, dist_c, sh_c
+
+    def march(self, rays, K):
+        """The samples of packed ray rows [R, 8 or 11] that lie in occupied cells, out of K lattice samples per
+        ray at the coarse sampler's unperturbed depths: (counts int32 [R], offsets int32 [R + 1], pts_c [n, 3],
+        z_c [n], dist_c [n], sh_c [n, 16] or None for rows without view directions). Ray r owns entries
+        [offsets[r], offsets[r + 1]) in ascending depth; dist_c is the distance to the next lattice sample
+        (1e10 after the last). One host read (the list's length) sizes the outputs."""
+        rays, t, counts, offsets, _, n = self._march_count(rays, K)
+        K = int(K)
+        pts_c, z_c, dist_c, sh_c = self._march_write(rays, t, K, counts, offsets, n, rays.shape[1] == 11)
+        self._last = (n, rays.shape[0] * K)
+        return counts, offsets, pts_c, z_c, dist_c, sh_c

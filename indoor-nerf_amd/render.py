@@ -397,7 +397,8 @@ def last_early_stop_counts():
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False, lindisp=False,
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
-                pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32):
+                pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
+                march=None, march_samples=512, march_points=1 << 21):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -406,7 +407,20 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     -log(eps) gets all-zero raw rows in every later slab; the result then also holds early_stop_samples
     (int32 [R], the leading samples of the final pass for which the ray was alive) and, with
     N_importance > 0, early_stop_samples0 (the coarse pass). Composes with occupancy. None (the default)
-    leaves the call as it is without it."""
+    leaves the call as it is without it.
+    march (an occupancy.OccupancyGrid; forward-only rendering): one pass over march_samples
+    (1..4096) samples per ray at the coarse sampler's unperturbed depths, through network_fine (network_fn
+    without one), of which only those inside the box and in an occupied cell are ever formed: a packed list
+    per ray, the field on the list (in slices of at most march_points points) and the compositing of the
+    list. The result is what masking sigma by grid.query in that dense render gives: rgb_map, depth_map,
+    acc_map, march_samples (int32 [R], the kept samples per ray) and rays_d; with retraw also the packed
+    raw [n, 4], pts [n, 3], z_vals [n] and march_offsets (int32 [R + 1]). N_samples and N_importance are not
+    used. None (the default) leaves the call as it is without it."""
+    if march is not None:
+        return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points,
+                                  embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
+                                  network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
+                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -527,6 +541,73 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     return ret
 
 
+def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, perturb, raw_noise_std, predict_normals,
+                 occupancy, early_stop):
+    """render_rays' refusals with march=, all before any launch."""
+    from .occupancy import OccupancyGrid, _check_modules, check_march_samples
+    from .sparse_field import NOT_IN_TRAINING, check_march_points
+    if not isinstance(grid, OccupancyGrid):
+        raise ValueError(f"render_rays: march must be an OccupancyGrid, got {type(grid).__name__}")
+    K = check_march_samples(march_samples, "render_rays: march")
+    check_march_points(march_points)
+    if occupancy is not None or early_stop is not None:
+        raise ValueError("render_rays: march does not combine with occupancy= (the march already masks by its grid) "
+                         "or early_stop= (rays are not stopped inside a march)")
+    if torch.is_grad_enabled():
+        raise ValueError(f"render_rays: march is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING['march']})")
+    if raw_noise_std > 0.:
+        raise ValueError("render_rays: march needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 at "
+                         "skipped samples)")
+    if perturb > 0.:
+        raise ValueError("render_rays: march needs perturb == 0 (the lattice is the unperturbed coarse sampling)")
+    if lindisp:
+        raise ValueError("render_rays: march needs lindisp=False (the lattice is linear in depth)")
+    if predict_normals or getattr(fn, "raw_channels", 4) != 4:
+        raise ValueError("render_rays: march does not support predict_normals or a normals head")
+    if embed_fn is not None:
+        _check_modules(embed_fn, fn, "render_rays: march")
+    return K
+
+
+def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
+                       retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
+                       predict_normals=False, occupancy=None, early_stop=None):
+    """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
+    the list (sparse_field.run_network_packed), the packed compositing."""
+    run_fn = network_fn if network_fine is None else network_fine
+    K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
+                     predict_normals, occupancy, early_stop)
+    if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
+        raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
+    from .sparse_field import MarchRequest
+    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K)
+    R, dev = rays.shape[0], rays.device
+    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True)
+    grid._last = (n, R * K)
+    f = dict(device=dev, dtype=torch.float32)
+    if n > 0:
+        req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
+        raw = network_query_fn(pts_c, rays[:, 8:11], run_fn)
+        del pts_c._nerf_sparse
+        if not req.used:   # a foreign query function ignores the attribute: never fall back silently
+            raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
+    else:
+        raw = torch.empty(0, 4, **f)
+    rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
+    if R > 0:
+        _lib.call("nerf_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z_c, "z_c"), _lib.ptr(dist_c, "dist_c"),
+                  _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n, int(bool(white_bkgd)),
+                  _lib.ptr(rgb_map, "rgb"), None, _lib.ptr(acc_map, "acc"), _lib.ptr(depth_map, "depth"), None,
+                  _lib.stream())
+    # restated for zero rays in _no_rays_result: keep the two in step
+    ret = dict(rgb_map=rgb_map, depth_map=depth_map, acc_map=acc_map, march_samples=counts, rays_d=rays_d)
+    if retraw:
+        ret.update(raw=raw, pts=pts_c, z_vals=z_c, march_offsets=offsets)
+    if DEBUG:
+        check_numerics(ret)
+    return ret
+
+
 def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
     """run_nerf.py:71-83."""
     all_ret = {}
@@ -615,9 +696,12 @@ def _missed_value(key, white_bkgd):
 
 
 def _no_rays_result(device, N_samples, N_importance=0, retraw=False, predict_normals=False, early_stop=None,
-                    network_fn=None, network_fine=None, **_):
+                    network_fn=None, network_fine=None, march=None, **_):
     """render_rays' result for zero rays, without a field call (every ray of the frame missed)."""
     f = dict(device=device, dtype=torch.float32)
+    if march is not None:   # _render_rays_march's entries (render() refuses retraw with march)
+        return dict(rgb_map=torch.empty(0, 3, **f), depth_map=torch.empty(0, **f), acc_map=torch.empty(0, **f),
+                    march_samples=torch.empty(0, device=device, dtype=torch.int32), rays_d=torch.empty(0, 3, **f))
     M = N_samples + N_importance
     fine = network_fn if network_fine is None else network_fine
     ret = {}
@@ -679,7 +763,13 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     crosses no occupied cell gets the background without a field call, every other ray places its samples
     between its first and its last occupied cell instead of over [near, far]. The extras then also hold
     ray_hit (bool) and ray_span ([near', far'] per ray). Composes with occupancy= and early_stop=. None (the
-    default) leaves the call as it is without it."""
+    default) leaves the call as it is without it.
+    march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
+    spans its own [near', far']. retraw is refused with march: the packed entries of several chunks do not
+    concatenate."""
+    if kwargs.get("march") is not None and kwargs.get("retraw"):
+        raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
+                         "concatenate; call render_rays on one chunk)")
     if ray_bounds is not None:
         _check_ray_bounds(ray_bounds)
     if c2w is not None:

@@ -1,5 +1,6 @@
 """The field call of the forward-only render paths that evaluate only some samples: an occupancy grid
-(occupancy.py), early ray termination (early_stop.py), or both.
+(occupancy.py), early ray termination (early_stop.py), or both; and the field
+call of a grid march over its packed list of kept samples (MarchRequest).
 
 render_rays attaches a SparseRequest to the point tensor of a pass; the fused run_network (field.py) hands
 the call to run_network_sparse. The kept samples are compacted in ascending order
@@ -14,7 +15,9 @@ from .hashgrid import SHEncoder
 from .occupancy import _check_modules
 
 # why each keyword is forward-only (render_rays' and run_network_sparse's refusals)
-NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training"}
+NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training",
+                   "march": "rays are not marched in training"}
+DEFAULT_MARCH_POINTS = 1 << 21
 
 
 class SparseRequest:
@@ -33,11 +36,67 @@ class SparseRequest:
         return "occupancy" if self.early is None else "early_stop"
 
 
+class MarchRequest:
+    """render_rays' request of a grid march (attached to the packed point tensor [n, 3] as `pts._nerf_sparse`):
+    the SH4 rows of the points' rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch.
+    run_network sets `used`, as for a SparseRequest."""
+    what = "march"
+
+    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS):
+        self.sh_c, self.max_points = sh_c, check_march_points(max_points)
+        self.used = False
+
+
+def check_march_points(m):
+    if isinstance(m, bool) or not isinstance(m, int) or m < 1:
+        raise ValueError(f"march: march_points must be a positive integer, got {m!r}")
+    if 16 * (m + 32) >= 2 ** 31:
+        raise ValueError(f"march: march_points {m} exceeds the MLP's 32-bit row indexing (16 (n + 32) < 2^31)")
+    return m
+
+
+def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+    """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
+    raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16) run over the list in
+    slices of at most req.max_points points; a point's result does not depend on its slice."""
+    from .field import _weights_struct
+    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 2 or req.sh_c is None:
+        raise ValueError("march: needs the fused field call (SHEncoder view encoding, viewdirs, packed inputs [n, 3])")
+    _check_modules(embed_fn, fn, "march")
+    if fn.raw_channels != 4:
+        raise ValueError("march: a normals head is not supported (run_network's box mask then lands on n_z, "
+                         "not on sigma, so a skipped sample is not a zero-weight sample)")
+    if torch.is_grad_enabled():
+        raise ValueError(f"march: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING['march']})")
+    if embed_fn.training:
+        embed_fn.current_step += 1
+    n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
+    if tuple(req.sh_c.shape) != (n, 16):
+        raise ValueError("march: SH rows of the request do not match the points")
+    f = dict(device=dev, dtype=torch.float32)
+    raw = torch.empty(n, 4, **f)
+    if n == 0:
+        return raw
+    pts = inputs.detach().float().contiguous()
+    weights = _weights_struct(fn.mlp_weights())
+    m = min(n, req.max_points)
+    feat, keep = torch.empty(L * m * 2, **f), torch.empty(m, device=dev, dtype=torch.bool)
+    for s0 in range(0, n, m):
+        k = min(m, n - s0)
+        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * 2], 2, 2 * k, keep[:k])
+        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"), 16,
+                  None, 1, _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"),
+                  None, None, None, 0, None, _lib.stream())
+    return raw
+
+
 def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     """run_network (field.py) for a SparseRequest: inputs [R, S, 3], viewdirs [R, 3] -> raw [R, S, 4] with
     the field evaluated at the kept samples only and zero rows elsewhere. Without early termination the call
     is one slab through req.grid.compact; with it, slabs of req.early's size front to back, nerf_ert_advance
     between them, and req.stop receives the stops."""
+    if isinstance(req, MarchRequest):
+        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req)
     from .field import _point_order, _weights_struct
     what = req.what
     if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 3:

@@ -25,9 +25,15 @@ of 32) and of both, next to occupancy= alone through the same grid; and, through
 the samples (32 + 64) placed inside the spans. Per variant: the share of rays dropped, the mean span over
 far - near, the frame time and the PSNR.
 
+With --march the same frame, process and method time grid ray marching instead (render(march=grid), csrc/march.hip,
+DESIGN.md §16): the dense 64 + 128 frame of the unchanged path, occupancy= alone and march= at 192, 512 and 1024
+lattice samples per ray, each through the grid of update()'s defaults, a grid with every cell set and the scene's
+own geometry grid. Per variant: the frame time, the points the field evaluated and the PSNR.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
+       python tools/render_time.py --march [--out profiles/march_render_time.json]
 """
 import argparse
 import ast
@@ -271,6 +277,86 @@ def main_ray_bounds(a):
     print(json.dumps(out))
 
 
+def main_march(a):
+    """The grid ray-marching table: see the module docstring."""
+    bbox, emb, coarse, fine, kw_test = trained_scene(a.iters)
+    gpu = torch.device("cuda:0")
+    lo, hi = blender_bbox()
+    new_grid = lambda: nerf.OccupancyGrid(bbox, resolution=a.resolution, device=gpu)  # noqa: E731
+    grids = {"default grid": new_grid().update(emb, [coarse, fine]), "full grid": new_grid(),
+             "geometry grid": new_grid()}
+    grids["full grid"].set_mask(np.ones((a.resolution,) * 3, bool))
+    grids["geometry grid"].set_mask(geometry_mask(lo, hi, a.resolution))
+
+    H = W = a.size
+    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
+    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
+    pose = torch.from_numpy(pose_spherical(np.linspace(-180, 180, 101)[34], -30.0, 4.0311))[:3, :4].to(gpu)
+
+    def frame(over):
+        with torch.no_grad():
+            return nerf.render(H, W, K, chunk=a.chunk, c2w=pose, **dict(kw_test, **over))
+
+    def timed(over):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        frame(over)
+        e1.record()
+        torch.cuda.synchronize()
+        return e0.elapsed_time(e1)
+
+    ro_np, rd_np = nerf.get_rays_np(H, W, K, pose.cpu().numpy())
+    target = torch.from_numpy(procedural_targets(np.ascontiguousarray(ro_np.reshape(-1, 3), np.float32),
+                                                 np.ascontiguousarray(rd_np.reshape(-1, 3), np.float32))).to(gpu)
+    psnr = lambda img: float(-10.0 * torch.log10(((img.reshape(-1, 3) - target) ** 2).mean()))  # noqa: E731
+
+    variants = [("dense", {})]
+    for gname, grid in grids.items():
+        variants.append((f"{gname}: occupancy alone", dict(occupancy=grid)))
+        variants += [(f"{gname}: march, K = {k}", dict(march=grid, march_samples=k)) for k in (192, 512, 1024)]
+
+    report = {}
+    for name, over in variants:         # one untimed frame per variant: PSNR and the points the field evaluated
+        grid, calls = over.get("occupancy"), []
+        if grid is not None:
+            compact = grid.compact
+
+            def recording(pts, viewdirs, spr, raw, grid=grid, compact=compact, calls=calls):
+                res = compact(pts, viewdirs, spr, raw)
+                calls.append(grid.last_counts())
+                return res
+            grid.compact = recording
+        out = frame(over)
+        if grid is not None:
+            del grid.compact
+        report[name] = {"psnr_db": psnr(out[0])}
+        if "march" in over:
+            n, total = int(out[3]["march_samples"].sum()), H * W * over["march_samples"]
+        elif grid is not None:
+            n, total = sum(c[0] for c in calls), sum(c[1] for c in calls)
+        else:
+            n = total = H * W * (kw_test["N_samples"] + kw_test["N_samples"] + kw_test["N_importance"])
+        report[name].update(evaluated_points=n, lattice_points=total, share=n / max(1, total))
+    for _, over in variants:            # warm-up of every variant
+        timed(over)
+    times = {name: [] for name, _ in variants}
+    for _ in range(a.frames):           # alternating
+        for name, over in variants:
+            times[name].append(timed(over))
+    for name, v in times.items():
+        report[name]["render_ms"] = {"median": float(np.median(v)), "min": float(np.min(v)), "max": float(np.max(v)),
+                                     "frames": len(v)}
+        report[name]["speedup_vs_dense"] = float(np.median(times["dense"]) / np.median(v))
+    out = {"scene": f"two-sphere scene, {a.iters} training iterations", "frame": [H, W], "chunk": a.chunk,
+           "N_samples": 64, "N_importance": 128, "grid_resolution": a.resolution,
+           "grid_occupied_fraction": {k: g.occupied_fraction() for k, g in grids.items()},
+           "variants": report, "device": torch.cuda.get_device_name(0)}
+    os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+    with open(a.out, "w") as fp:
+        json.dump(out, fp, indent=1)
+    print(json.dumps(out))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -281,10 +367,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--early-stop", action="store_true", help="time early ray termination (DESIGN.md §14)")
     ap.add_argument("--ray-bounds", action="store_true", help="time per-ray sample bounds (DESIGN.md §15)")
+    ap.add_argument("--march", action="store_true", help="time grid ray marching (DESIGN.md §16)")
     a = ap.parse_args()
     if a.out is None:
         a.out = ("profiles/early_stop_render_time.json" if a.early_stop else
-                 "profiles/ray_bounds_render_time.json" if a.ray_bounds else "bench_out/render_time.json")
+                 "profiles/ray_bounds_render_time.json" if a.ray_bounds else
+                 "profiles/march_render_time.json" if a.march else "bench_out/render_time.json")
+    if a.march:
+        return main_march(a)
     if a.early_stop:
         return main_early_stop(a)
     if a.ray_bounds:
