@@ -45,6 +45,14 @@ def check_march_samples(K, what):
     return int(K)
 
 
+def _packed_rows(rays, method):
+    """Packed ray rows as OccupancyGrid.`method` takes them (fp32, contiguous, detached), or ValueError."""
+    if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] not in (8, 11):
+        raise ValueError(f"OccupancyGrid.{method}: rays must be packed rows [R, 8] or [R, 11] (o, d, near, far"
+                         f"[, viewdir]), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}")
+    return rays.detach().float().contiguous()
+
+
 class OccupancyGrid:
     """Density bitfield over `bounding_box`: resolution^3 cells, cell (ix, iy, iz) = bit
     (ix*res + iy)*res + iz (csrc/occupancy.hip has the cell rule). A new grid is empty."""
@@ -177,10 +185,7 @@ class OccupancyGrid:
 
     # ---- per-ray sample bounds (csrc/ray_span.hip) --------------------------------
     def _span(self, rays):
-        if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] not in (8, 11):
-            raise ValueError("OccupancyGrid.ray_span: rays must be packed rows [R, 8] or [R, 11] (o, d, near, far"
-                             f"[, viewdir]), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}")
-        rays = rays.detach().float().contiguous()
+        rays = _packed_rows(rays, "ray_span")
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
         hit = torch.empty(R, dtype=torch.bool, device=dev)
         span = torch.empty(R, 2, dtype=torch.float32, device=dev)
@@ -218,11 +223,8 @@ class OccupancyGrid:
     def _march_count(self, rays, K):
         """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n)."""
         from .render import _linspace
-        if not torch.is_tensor(rays) or rays.dim() != 2 or rays.shape[1] not in (8, 11):
-            raise ValueError("OccupancyGrid.march: rays must be packed rows [R, 8] or [R, 11] (o, d, near, far"
-                             f"[, viewdir]), got {tuple(rays.shape) if torch.is_tensor(rays) else type(rays).__name__}")
+        rays = _packed_rows(rays, "march")
         K = check_march_samples(K, "OccupancyGrid.march")
-        rays = rays.detach().float().contiguous()
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
         if R * K > 2 ** 31 - 1:
             raise ValueError(f"OccupancyGrid.march: {R} rays x {K} samples exceed 2^31 - 1; use a smaller chunk")

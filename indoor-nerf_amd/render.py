@@ -426,13 +426,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         from .early_stop import check_params
         early = check_params(early_stop, early_stop_slab)
     if early is not None or occupancy is not None:
-        from .sparse_field import NOT_IN_TRAINING
-        what = "occupancy" if early is None else "early_stop"
-        if torch.is_grad_enabled():
-            raise ValueError(f"render_rays: {what} is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
-        if raw_noise_std > 0.:
-            raise ValueError(f"render_rays: {what} needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 "
-                             "at skipped samples)")
+        from .sparse_field import check_forward_only
+        check_forward_only("occupancy" if early is None else "early_stop", "render_rays", raw_noise_std)
     rays = ray_batch.detach().float().contiguous()
     R, C = rays.shape
     dev = rays.device
@@ -545,7 +540,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
                  occupancy, early_stop):
     """render_rays' refusals with march=, all before any launch."""
     from .occupancy import OccupancyGrid, _check_modules, check_march_samples
-    from .sparse_field import NOT_IN_TRAINING, check_march_points
+    from .sparse_field import check_forward_only, check_march_points
     if not isinstance(grid, OccupancyGrid):
         raise ValueError(f"render_rays: march must be an OccupancyGrid, got {type(grid).__name__}")
     K = check_march_samples(march_samples, "render_rays: march")
@@ -553,11 +548,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
     if occupancy is not None or early_stop is not None:
         raise ValueError("render_rays: march does not combine with occupancy= (the march already masks by its grid) "
                          "or early_stop= (rays are not stopped inside a march)")
-    if torch.is_grad_enabled():
-        raise ValueError(f"render_rays: march is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING['march']})")
-    if raw_noise_std > 0.:
-        raise ValueError("render_rays: march needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 at "
-                         "skipped samples)")
+    check_forward_only("march", "render_rays", raw_noise_std)
     if perturb > 0.:
         raise ValueError("render_rays: march needs perturb == 0 (the lattice is the unperturbed coarse sampling)")
     if lindisp:
@@ -727,11 +718,10 @@ def _no_rays_result(device, N_samples, N_importance=0, retraw=False, predict_nor
 
 def _check_ray_bounds(grid):
     from .occupancy import OccupancyGrid
+    from .sparse_field import check_forward_only
     if not isinstance(grid, OccupancyGrid):
         raise ValueError(f"render: ray_bounds must be an OccupancyGrid, got {type(grid).__name__}")
-    if torch.is_grad_enabled():
-        raise ValueError("render: ray_bounds is forward-only (call under torch.no_grad(); rays are not bounded "
-                         "in training)")
+    check_forward_only("ray_bounds", "render")
 
 
 def _render_bounded(rays, chunk, grid, kwargs):

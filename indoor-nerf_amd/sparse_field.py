@@ -14,9 +14,9 @@ from .early_stop import _LAST, tau_max_of
 from .hashgrid import SHEncoder
 from .occupancy import _check_modules
 
-# why each keyword is forward-only (render_rays' and run_network_sparse's refusals)
+# why each keyword is forward-only (check_forward_only's and _begin_field_call's refusals)
 NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training",
-                   "march": "rays are not marched in training"}
+                   "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -55,21 +55,38 @@ def check_march_points(m):
     return m
 
 
+def check_forward_only(what, prefix, raw_noise_std=0.):
+    """The refusals every forward-only keyword `what` of `prefix` (render_rays, render) shares: no gradients, no
+    raw noise."""
+    if torch.is_grad_enabled():
+        raise ValueError(f"{prefix}: {what} is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+    if raw_noise_std > 0.:
+        raise ValueError(f"{prefix}: {what} needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 at skipped "
+                         "samples)")
+
+
+def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embeddirs_fn):
+    """What run_network_sparse and run_network_packed do first: their refusals, all before any launch (inputs_ok:
+    the inputs are what shape_words says), then the step count of a training-mode encoder."""
+    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or not inputs_ok:
+        raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
+    _check_modules(embed_fn, fn, what)
+    if fn.raw_channels != 4:
+        raise ValueError(f"{what}: a normals head is not supported (run_network's box mask then lands on n_z, "
+                         "not on sigma, so a skipped sample is not a zero-weight sample)")
+    if torch.is_grad_enabled():
+        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+    if embed_fn.training:
+        embed_fn.current_step += 1
+
+
 def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
     raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16) run over the list in
     slices of at most req.max_points points; a point's result does not depend on its slice."""
     from .field import _weights_struct
-    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 2 or req.sh_c is None:
-        raise ValueError("march: needs the fused field call (SHEncoder view encoding, viewdirs, packed inputs [n, 3])")
-    _check_modules(embed_fn, fn, "march")
-    if fn.raw_channels != 4:
-        raise ValueError("march: a normals head is not supported (run_network's box mask then lands on n_z, "
-                         "not on sigma, so a skipped sample is not a zero-weight sample)")
-    if torch.is_grad_enabled():
-        raise ValueError(f"march: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING['march']})")
-    if embed_fn.training:
-        embed_fn.current_step += 1
+    _begin_field_call("march", inputs.dim() == 2 and req.sh_c is not None, "packed inputs [n, 3]", viewdirs, fn,
+                      embed_fn, embeddirs_fn)
     n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
     if tuple(req.sh_c.shape) != (n, 16):
         raise ValueError("march: SH rows of the request do not match the points")
@@ -99,16 +116,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
         return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req)
     from .field import _point_order, _weights_struct
     what = req.what
-    if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or inputs.dim() != 3:
-        raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, inputs [R, S, 3])")
-    _check_modules(embed_fn, fn, what)
-    if fn.raw_channels != 4:
-        raise ValueError(f"{what}: a normals head is not supported (run_network's box mask then lands on n_z, "
-                         "not on sigma, so a skipped sample is not a zero-weight sample)")
-    if torch.is_grad_enabled():
-        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
-    if embed_fn.training:
-        embed_fn.current_step += 1
+    _begin_field_call(what, inputs.dim() == 3, "inputs [R, S, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
     R, S = inputs.shape[0], inputs.shape[1]
     P, dev, L = R * S, inputs.device, embed_fn.n_levels
     if 16 * (P + 32) >= 2 ** 31:

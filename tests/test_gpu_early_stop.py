@@ -1,12 +1,10 @@
 """Early ray termination for forward-only rendering (csrc/early_stop.hip, early_stop.py),
 needs an MI355X.
 
-Scene of test_gpu_occupancy.py (blender_bbox, tables uniform +-0.05, finest_res 512, 32 + 32 samples, white
-background, eval mode, two 12 x 16 frames with near = 0.5, far = 9.0), with one change: that random field has
-relu(sigma) * delta summing to only 0.01 - 0.04 per ray, so nothing would ever terminate, and the fixture
-multiplies row 0 of sigma_net.1.weight (the sigma row; there are no biases, so this scales sigma exactly)
-of both networks by SIGMA_SCALE = 500 (the dense optical depth after S / 2 samples then has its 0.75
-quantile near 7, so that eps lies well inside (1e-6, 0.1); at 1000 it is 14.2 and eps 6.8e-7 falls outside).
+The scene of forward_only.py (build_scene), with one change: that random field has relu(sigma) * delta summing
+to only 0.01 - 0.04 per ray, so nothing would ever terminate, and the fixture multiplies the sigma row of both
+networks by SIGMA_SCALE = 500 (the dense optical depth after S / 2 samples then has its 0.75 quantile near 7, so
+that eps lies well inside (1e-6, 0.1); at 1000 it is 14.2 and eps 6.8e-7 falls outside).
 
 eps is calibrated from the dense render, never from the path under test: tau_q is the QUANTILE = 0.75
 quantile, over the rays of both frames, of the dense coarse optical depth after S / 2 samples (fp64, from
@@ -21,38 +19,25 @@ path writes a zero row there, so the masked reference multiplies the dense raw b
 well (the query of a one-cell grid with its bit set), and raw is compared after adding 0.0 to both sides
 (a negative value times 0 is -0.0).
 """
-import ast
 import math
 
 import numpy as np
 import pytest
 import torch
 
-from tables import blender_bbox, closed_form_table, convergence_rays
+from forward_only import (FAR, H, NEAR, W, assert_maps_equal, ball_mask, bits_equal, build_scene, np_cells, random_mask,
+                          run_compact, two_sphere_scene)
+from tables import blender_bbox
 
 pytestmark = pytest.mark.gpu
 
-H, W = 12, 16
 S = 32
-NEAR, FAR = 0.5, 9.0
 SIGMA_SCALE = 500.0
 QUANTILE = 0.75
-MAPS = ("rgb", "depth", "acc", "rgb0", "depth0", "acc0", "z_std", "sparsity_loss", "sparsity_loss0", "raw")
 F0 = np.float32(0.0)
 
 
 # ---------------------------------------------------------------- NumPy restatements
-def np_cells(pts, lo, hi, res):
-    """The cell rule of csrc/occupancy.hip in NumPy fp32: (linear cell id, inside the box)."""
-    pts, lo, hi = (np.asarray(a, np.float32) for a in (pts, lo, hi))
-    cell = ((hi - lo) / np.float32(res)).astype(np.float32)
-    xc = np.minimum(np.maximum(pts, lo), hi)
-    base = np.floor((xc - lo) / cell).astype(np.int64)
-    idx = np.minimum(base, res - 1)
-    inside = (pts == np.maximum(np.minimum(pts, hi), lo)).all(-1)
-    return (idx[:, 0] * res + idx[:, 1]) * res + idx[:, 2], inside
-
-
 def np_advance(sigma, z, rays_d, s0, s1, tau_max, tau, alive, stop):
     """The rule of csrc/early_stop.hip for one slab in NumPy fp32: every operation below is one correctly
     rounded float32 operation per ray, the samples strictly in order. -> (tau, alive, stop)."""
@@ -91,68 +76,11 @@ def coarse_z(n_rays):
     return np.tile(z, (n_rays, 1))
 
 
-def random_mask(res):
-    return np.random.default_rng(res).random((res, res, res)) < 0.5
-
-
-def ball_mask(res=16, radius=0.35):
-    c = (np.arange(res) + 0.5) / res * 2.0 - 1.0
-    x, y, z = np.meshgrid(c, c, c, indexing="ij")
-    return np.sqrt(x * x + y * y + z * z) <= radius
-
-
-def bits_equal(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
-
-
-def assert_maps_equal(got, ref, what, raw_plus_zero=False):
-    for k in MAPS:
-        if k not in ref:
-            continue
-        a, b = got[k], ref[k]
-        if k == "raw" and raw_plus_zero:
-            a, b = a + 0.0, b + 0.0     # -0.0 (negative x 0 in the reference) -> +0.0, nothing else changes
-        assert bits_equal(a, b), f"{what}: {k} differs in {int((a != b).sum())} values"
-
-
 # ---------------------------------------------------------------- scene
 @pytest.fixture(scope="module")
 def scene(nerf, gpu):
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    args = nerf.make_args(bounding_box=bbox, finest_res=512, N_samples=S, N_importance=32, white_bkgd=True)
-    torch.manual_seed(0)
-    _, kw, _, _, _ = nerf.create_nerf(args, device=gpu)
-    kw.update(near=NEAR, far=FAR)
-    emb = kw["embed_fn"]
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        for e in emb.embeddings:
-            e.weight.copy_((torch.rand(e.weight.shape, generator=g) * 2 - 1) * 0.05)
-        for net in (kw["network_fn"], kw["network_fine"]):
-            net.sigma_net[1].weight[0].mul_(SIGMA_SCALE)
-    for m in (kw["network_fn"], kw["network_fine"], emb):
-        m.eval()
-    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
-    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
-    poses = [nerf.pose_spherical(a, -30.0, 4.0) for a in (-40.0, 75.0)]
-    cache = {}
-
-    def frame(i, chunk=4096, **over):
-        """One frame's maps; the dense ones (none of the new keywords, the package's own query function) are cached."""
-        plain = not any(k in over for k in ("occupancy", "network_query_fn", "early_stop"))
-        key = (i, chunk, tuple(sorted(over.items()))) if plain else None
-        if key in cache:
-            return cache[key]
-        with torch.no_grad():
-            rgb, depth, acc, ex = nerf.render(H, W, K, chunk=chunk, c2w=poses[i][:3, :4].to(gpu), retraw=True,
-                                              **dict(kw, **over))
-        out = dict(ex, rgb=rgb, depth=depth, acc=acc)
-        if key is not None:
-            cache[key] = out
-        return out
-
+    sc = build_scene(nerf, gpu, SIGMA_SCALE)
+    bbox, frame, poses = sc["bbox"], sc["frame"], sc["poses"]
     box = nerf.OccupancyGrid(bbox, resolution=1, device=gpu)     # query() = inside the box
     box.set_mask(np.ones((1, 1, 1), bool))
     ball = nerf.OccupancyGrid(bbox, resolution=16, device=gpu)
@@ -188,8 +116,7 @@ def scene(nerf, gpu):
         early, full = float((stop < S).mean()), int((stop == S).sum())
         print(f"pose {i}: NumPy stops at K = 8 {sorted(set(stop.tolist()))}, {100 * early:.0f} % stop early, {full} reach S")
         assert len(set(stop.tolist())) >= 3 and early >= 0.2 and full >= 5, "fixture conditions"
-    return dict(lo=lo, hi=hi, bbox=bbox, kw=kw, emb=emb, frame=frame, K=K, poses=poses, eps=eps, tau_max=tau_max,
-                dense=dense, box=box, grids={"none": None, "ball16": ball, "random5": rand})
+    return dict(sc, eps=eps, tau_max=tau_max, dense=dense, box=box, grids={"none": None, "ball16": ball, "random5": rand})
 
 
 def masked_query_fn(scene, stops, grid):
@@ -273,27 +200,6 @@ def test_advance_matches_numpy_rule(nerf, gpu, R, n, K):
 
 
 # ---------------------------------------------------------------- 2. the compaction
-def run_compact(L, gpu, pts, R, n, s0, s1, alive, sh_rays, viewdirs, lo, hi, grid, raw):
-    i32, f = dict(device=gpu, dtype=torch.int32), dict(device=gpu, dtype=torch.float32)
-    cand = R * (s1 - s0)
-    count = torch.full((1,), -1, **i32)
-    ws = torch.empty(int(L.load().nerf_ert_compact_workspace_bytes(cand)) // 4, **i32)
-    bmin, bmax = L.host_f32(lo), L.host_f32(hi)
-
-    def run(stages, cap, rows, pts_c, sh_c):
-        L.call("nerf_ert_compact", L.ptr(pts), R, n, s0, s1, L.ptr(alive, "alive", torch.uint8, True),
-               L.ptr(sh_rays, "sh", allow_none=True), L.ptr(viewdirs, "dirs", allow_none=True), bmin, bmax,
-               1 if grid is None else grid.resolution, None if grid is None else grid._bits(), stages, cap,
-               L.ptr(rows, "rows", torch.int32, True), L.ptr(count, "count", torch.int32),
-               L.ptr(pts_c, "pts_c", allow_none=True), L.ptr(sh_c, "sh_c", allow_none=True), L.ptr(raw),
-               L.ptr(ws, "ws", torch.int32), ws.numel() * 4, L.stream())
-    run(1, 0, None, None, None)
-    k = int(count.item())
-    rows, pts_c, sh_c = torch.empty(k, **i32), torch.empty(k, 3, **f), torch.empty(k, 16, **f)
-    run(2, k, rows if k else None, pts_c if k else None, sh_c if k else None)
-    return rows, pts_c, sh_c
-
-
 @pytest.mark.parametrize("with_grid", [False, True])
 @pytest.mark.parametrize("R", [1, 7, 193])
 def test_compact_matches_numpy(nerf, gpu, R, with_grid):
@@ -433,7 +339,7 @@ def test_error_bound(nerf, gpu, scene, which_eps):
                 over = {} if two_pass else {"N_importance": 0}
                 dense = scene["frame"](i, **over)
                 got = scene["frame"](i, early_stop=eps, early_stop_slab=K, **over)
-                rgb, acc = ("rgb0", "acc0") if two_pass else ("rgb", "acc")
+                rgb, acc = ("rgb0", "acc0") if two_pass else ("rgb_map", "acc_map")
                 e_rgb = float((got[rgb] - dense[rgb]).abs().max())
                 d_acc = dense[acc] - got[acc]
                 stopped = float((got["early_stop_samples0" if two_pass else "early_stop_samples"] < S).float().mean())
@@ -492,54 +398,13 @@ def test_trained_scene_psnr_within_0p1_db(nerf, gpu, golden):
     grid of the defaults: PSNR of the held-out and the novel rays against the procedural targets within
     0.1 dB of the dense render (the project's parity bar; at an RMSE near 0.1 a
     per-pixel change of 1e-3 moves PSNR by at most about 0.09 dB)."""
-    g = golden("f19_converge")
-    c = ast.literal_eval(str(g["config"]))
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    emb = nerf.HashEmbedder(bbox, finest_resolution=1024).to(gpu)
-    table = closed_form_table(scale=c["table_scale"], salt=c["table_salt"])
+    ts = two_sphere_scene(nerf, gpu, golden("f19_converge"))
+    psnr_of = ts.psnr_of
+    before, _ = psnr_of(*ts.ev)
+    ts.train(300)
+    grid = nerf.OccupancyGrid(ts.bbox, device=gpu).update(ts.emb, [ts.coarse, ts.fine])
 
-    def net(prefix):
-        m = nerf.NeRFSmall(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-                           input_ch=32, input_ch_views=16).to(gpu)
-        with torch.no_grad():
-            for k, p in m.named_parameters():
-                p.copy_(torch.from_numpy(g[prefix + k.replace(".", "_")]))
-        return m
-
-    coarse, fine = net("coarse0_"), net("fine0_")
-    with torch.no_grad():
-        for i, e in enumerate(emb.embeddings):
-            e.weight.copy_(torch.from_numpy(table[i]))
-    sh = nerf.SHEncoder()
-    nqf = lambda inputs, viewdirs, fn: nerf.run_network(inputs, viewdirs, fn, emb, sh)  # noqa: E731
-    kw = dict(network_query_fn=nqf, perturb=1.0, N_importance=128, network_fine=fine, N_samples=64,
-              network_fn=coarse, embed_fn=emb, use_viewdirs=True, white_bkgd=True, raw_noise_std=0.0,
-              predict_normals=False, ndc=False, lindisp=False, near=2.0, far=6.0, pytest=True)
-    kw_test = dict(kw, perturb=0.0, pytest=False)
-    args = nerf.make_args(lrate=c["lrate"], lrate_decay=c["lrate_decay"], sparse_loss_weight=c["sparsity"],
-                          tv_loss_weight=0.0, N_samples=64, N_importance=128, white_bkgd=True)
-    (ro, rd, rgb), ev, nv = convergence_rays()
-    ro, rd, rgb = (torch.from_numpy(a).to(gpu) for a in (ro, rd, rgb))
-    opt = nerf.RAdam([{"params": list(coarse.parameters()) + list(fine.parameters()), "weight_decay": 1e-6},
-                      {"params": list(emb.parameters()), "eps": 1e-15}], lr=c["lrate"], betas=(0.9, 0.99))
-
-    def psnr_of(o, d, target, **over):
-        with torch.no_grad():
-            out, _, _, ex = nerf.render(800, 800, None, rays=(o, d), **dict(kw_test, **over))
-            return (-10.0 * torch.log10(((out - target) ** 2).mean())).item(), ex
-
-    ev, nv = ([torch.from_numpy(a).to(gpu) for a in part] for part in (ev, nv))
-    before, _ = psnr_of(*ev)
-    rng = np.random.RandomState(100)
-    for it in range(1, 301):
-        idx = torch.from_numpy(rng.choice(ro.shape[0], c["R"], replace=False).astype(np.int64)).to(gpu)
-        nerf.train_step((ro[idx], rd[idx]), rgb[idx], kw, opt, args, it)
-    for m in (coarse, fine, emb):
-        m.eval()
-    grid = nerf.OccupancyGrid(bbox, device=gpu).update(emb, [coarse, fine])
-
-    for name, (o, d, t) in (("held-out", ev), ("novel", nv)):
+    for name, (o, d, t) in (("held-out", ts.ev), ("novel", ts.nv)):
         dense, _ = psnr_of(o, d, t)
         assert name != "held-out" or dense > before + 3.0, "fixture: the scene should have been learnt"
         for label, over in (("no grid", {}), ("default grid", {"occupancy": grid})):

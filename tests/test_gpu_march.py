@@ -1,8 +1,7 @@
 """Grid ray marching for forward-only rendering (csrc/march.hip, render_rays(march=)), needs
 an MI355X.
 
-Scene of test_gpu_occupancy.py (blender_bbox, tables uniform +-0.05, finest_res 512, white background, eval
-mode, two 12 x 16 frames with near = 0.5, far = 9.0) with the sigma row of both networks scaled by
+The scene of forward_only.py (build_scene) with the sigma row of both networks scaled by
 SIGMA_SCALE = 500 as test_gpu_early_stop.py does, so that rays through occupied cells become opaque.
 
 What is exact and what is not: the packed lists (counts, offsets, positions, depths, distances) are the NumPy
@@ -19,16 +18,16 @@ identical NaN pattern. A dropped sample, a wrong dist or a lost carry moves the 
 Measured on the MI355X (test_packed_composite_is_the_dense_kernel, all ten cases together): 0 of 164 924
 entries (rgb, disp, acc, depth, weights) are not bit-identical; the test prints the number.
 """
+import functools
+
 import numpy as np
 import pytest
 import torch
 
-from tables import blender_bbox
+from forward_only import FAR, H, NEAR, W, ball_mask, bits_equal, build_scene, np_query, random_mask, scatter_back
 
 pytestmark = pytest.mark.gpu
 
-H, W = 12, 16
-NEAR, FAR = 0.5, 9.0
 SIGMA_SCALE = 500.0
 f32 = np.float32
 MAP_ATOL = 2e-6          # rgb, acc
@@ -36,34 +35,6 @@ DEPTH_RTOL = 4e-6        # depth, disp (where finite; identical NaN pattern)
 
 
 # ---------------------------------------------------------------- NumPy restatements
-def np_cells(pts, lo, hi, res):
-    """The cell rule of csrc/occupancy.hip in NumPy fp32: (linear cell id, inside the box)."""
-    pts, lo, hi = (np.asarray(a, np.float32) for a in (pts, lo, hi))
-    cell = ((hi - lo) / np.float32(res)).astype(np.float32)
-    xc = np.minimum(np.maximum(pts, lo), hi)
-    base = np.floor((xc - lo) / cell).astype(np.int64)
-    idx = np.minimum(base, res - 1)
-    inside = (pts == np.maximum(np.minimum(pts, hi), lo)).all(-1)
-    return (idx[:, 0] * res + idx[:, 1]) * res + idx[:, 2], inside
-
-
-def np_query(pts, lo, hi, mask):
-    with np.errstate(invalid="ignore"):
-        cid, inside = np_cells(pts, lo, hi, mask.shape[0])
-    cid = np.where(inside, cid, 0)          # a NaN point has no cell; it is outside
-    return inside & mask.reshape(-1)[cid]
-
-
-def random_mask(res):
-    return np.random.default_rng(res).random((res, res, res)) < 0.5
-
-
-def ball_mask(res=16, radius=0.35):
-    c = (np.arange(res) + 0.5) / res * 2.0 - 1.0
-    x, y, z = np.meshgrid(c, c, c, indexing="ij")
-    return np.sqrt(x * x + y * y + z * z) <= radius
-
-
 def np_lattice(rays, K):
     """The lattice of packed rows in fp32, every operation rounded: z [R, K], pts [R, K, 3], dist [R, K]."""
     rays = np.asarray(rays, f32)
@@ -81,11 +52,6 @@ def np_march(rays, K, lo, hi, mask):
     counts = keep.sum(-1).astype(np.int32)
     offsets = np.concatenate([[0], np.cumsum(counts)]).astype(np.int32)
     return keep, counts, offsets, pts[keep], z[keep], dist[keep]
-
-
-def bits_equal(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 def np_bits_equal(a, b):
@@ -110,55 +76,13 @@ def hand_rays(lo, hi):
 
 @pytest.fixture(scope="module")
 def scene(nerf, gpu):
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    args = nerf.make_args(bounding_box=bbox, finest_res=512, N_samples=32, N_importance=32, white_bkgd=True)
-    torch.manual_seed(0)
-    _, kw, _, _, _ = nerf.create_nerf(args, device=gpu)
-    kw.update(near=NEAR, far=FAR)
-    emb = kw["embed_fn"]
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        for e in emb.embeddings:
-            e.weight.copy_((torch.rand(e.weight.shape, generator=g) * 2 - 1) * 0.05)
-        for net in (kw["network_fn"], kw["network_fine"]):
-            net.sigma_net[1].weight[0].mul_(SIGMA_SCALE)
-    for m in (kw["network_fn"], kw["network_fine"], emb):
-        m.eval()
-    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
-    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
-    poses = [nerf.pose_spherical(a, -30.0, 4.0) for a in (-40.0, 75.0)]
-    from indoor_nerf_amd.render import _pack_rays as pack
-
-    def packed(i):
-        """The packed rows [H * W, 11] of frame i, as render() builds them."""
-        ro, rd = nerf.get_rays(H, W, K, poses[i][:3, :4].to(gpu))
-        return pack(H, W, K, ro, rd, kw["near"], kw["far"], kw["ndc"], kw["use_viewdirs"])
-
-    def grid_of(mask):
-        grid = nerf.OccupancyGrid(bbox, resolution=mask.shape[0], device=gpu)
-        grid.set_mask(mask)
-        return grid
-
-    def frame(i, chunk=4096, retraw=False, **over):
-        with torch.no_grad():
-            rgb, depth, acc, ex = nerf.render(H, W, K, chunk=chunk, c2w=poses[i][:3, :4].to(gpu), retraw=retraw,
-                                              **dict(kw, **over))
-        return dict(ex, rgb_map=rgb, depth_map=depth, acc_map=acc)
-
-    def ray_kw(**over):
-        """kw for render_rays / batchify_rays (render()'s own keywords removed)."""
-        out = dict(kw, **over)
-        for k in ("near", "far", "ndc", "use_viewdirs"):
-            out.pop(k)
-        return out
-
+    sc = build_scene(nerf, gpu, SIGMA_SCALE)
+    lo, hi, packed = sc["lo"], sc["hi"], sc["packed"]
     frame_rays = np.concatenate([packed(i).cpu().numpy() for i in (0, 1)])
     hand = hand_rays(lo, hi)
     vd = hand[:, 3:6] / np.linalg.norm(hand[:, 3:6], axis=-1, keepdims=True)
     pool = np.concatenate([np.concatenate([hand, vd.astype(f32)], -1), frame_rays]).astype(f32)
-    return dict(lo=lo, hi=hi, bbox=bbox, kw=kw, K=K, poses=poses, packed=packed, grid_of=grid_of, frame=frame,
-                ray_kw=ray_kw, pool=pool)
+    return dict(sc, frame=functools.partial(sc["frame"], retraw=False), pool=pool)
 
 
 MASKS = {"empty": lambda: np.zeros((4, 4, 4), bool), "full4": lambda: np.ones((4, 4, 4), bool),
@@ -369,9 +293,6 @@ def test_march_2048_samples(nerf, gpu, scene, oracle):
 
 
 # ---------------------------------------------------------------- 5. composition with ray_bounds
-FILL = {"rgb_map": 1.0, "depth_map": float("nan")}    # white background
-
-
 def test_march_with_ray_bounds_is_the_hand_composition(nerf, gpu, scene):
     grid = scene["grid_of"](ball_mask())
     for i in (0, 1):
@@ -383,10 +304,8 @@ def test_march_with_ray_bounds_is_the_hand_composition(nerf, gpu, scene):
                 part = nerf.batchify_rays(rays_c, chunk, march=grid, march_samples=64, **scene["ray_kw"]())
             got = scene["frame"](i, chunk=chunk, ray_bounds=grid, march=grid, march_samples=64)
             assert sorted(got) == sorted(list(part) + ["ray_hit", "ray_span"])
-            for k, v in part.items():
-                full = torch.full((H * W,) + tuple(v.shape[1:]), FILL.get(k, 0), device=v.device, dtype=v.dtype)
-                full[hit] = v
-                assert bits_equal(got[k], full.reshape((H, W) + tuple(v.shape[1:]))), f"pose {i} chunk {chunk}: {k}"
+            for k, full in scatter_back(part, hit).items():
+                assert bits_equal(got[k], full), f"pose {i} chunk {chunk}: {k}"
             assert bool((got["march_samples"][~got["ray_hit"]] == 0).all())
             assert bool((got["march_samples"][got["ray_hit"]] > 0).any())
 

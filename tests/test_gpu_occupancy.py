@@ -1,11 +1,9 @@
 """Occupancy-grid empty-space skipping (csrc/occupancy.hip, occupancy.py), needs an MI355X.
 
-Scene of test_gpu_render_path.py (blender_bbox, tables uniform +-0.05, finest_res 512, 32 + 32 samples,
-white background, eval mode), two 12 x 16 frames with near = 0.5, far = 9.0, so that about a tenth of the
-coarse samples lie outside the box. Tensors are compared through their int32 views (identical NaNs
-compare equal): the occupancy path is exact masking, not an approximation — the hash gather and the MLP
-outputs of a point do not depend on its tile or row (test_gpu_coarse_reuse.py, test_gpu_sh_rows.py), and
-a zero raw row is what masking gives.
+The scene of forward_only.py (build_scene), rendered in chunks of 100 rays unless a test says otherwise.
+Tensors are compared through their int32 views (identical NaNs compare equal): the occupancy path is exact
+masking, not an approximation — the hash gather and the MLP outputs of a point do not depend on its tile or
+row (test_gpu_coarse_reuse.py, test_gpu_sh_rows.py), and a zero raw row is what masking gives.
 
 Two notes on the raw comparisons:
   * full grid vs the dense path: every composited map is bit-identical, but the dense raw keeps the
@@ -17,85 +15,23 @@ Two notes on the raw comparisons:
     composites exactly like +0.0 (sigmoid(-0) = 0.5, relu(-0) = 0) but has another bit pattern, so raw
     itself is compared after adding 0.0 to both sides (-0 -> +0, every other value unchanged).
 """
-import ast
+import functools
 
 import numpy as np
 import pytest
 import torch
 
-from tables import blender_bbox, closed_form_table, convergence_rays
+from forward_only import (H, W, assert_maps_equal, ball_mask, bits_equal, build_scene, np_cells, np_query, random_mask,
+                          two_sphere_scene)
 
 pytestmark = pytest.mark.gpu
-
-H, W = 12, 16
-MAPS = ("rgb", "depth", "acc", "rgb0", "depth0", "acc0", "z_std", "sparsity_loss", "sparsity_loss0", "raw")
-
-
-def np_cells(pts, lo, hi, res):
-    """The cell rule of csrc/occupancy.hip in NumPy fp32: (linear cell id, inside the box)."""
-    pts, lo, hi = (np.asarray(a, np.float32) for a in (pts, lo, hi))
-    cell = ((hi - lo) / np.float32(res)).astype(np.float32)
-    xc = np.minimum(np.maximum(pts, lo), hi)
-    base = np.floor((xc - lo) / cell).astype(np.int64)
-    idx = np.minimum(base, res - 1)
-    inside = (pts == np.maximum(np.minimum(pts, hi), lo)).all(-1)
-    return (idx[:, 0] * res + idx[:, 1]) * res + idx[:, 2], inside
-
-
-def np_query(pts, lo, hi, mask):
-    cid, inside = np_cells(pts, lo, hi, mask.shape[0])
-    return inside & mask.reshape(-1)[cid]
-
-
-def random_mask(res):
-    return np.random.default_rng(res).random((res, res, res)) < 0.5
-
-
-def ball_mask(res=16, radius=0.35):
-    c = (np.arange(res) + 0.5) / res * 2.0 - 1.0
-    x, y, z = np.meshgrid(c, c, c, indexing="ij")
-    return np.sqrt(x * x + y * y + z * z) <= radius
-
-
-def bits_equal(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    return a.shape == b.shape and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 @pytest.fixture(scope="module")
 def scene(nerf, gpu):
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    args = nerf.make_args(bounding_box=bbox, finest_res=512, N_samples=32, N_importance=32, white_bkgd=True)
-    torch.manual_seed(0)
-    _, kw, _, _, _ = nerf.create_nerf(args, device=gpu)
-    kw.update(near=0.5, far=9.0)
-    emb = kw["embed_fn"]
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        for e in emb.embeddings:
-            e.weight.copy_((torch.rand(e.weight.shape, generator=g) * 2 - 1) * 0.05)
-    for m in (kw["network_fn"], kw["network_fine"], emb):
-        m.eval()
-    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
-    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
-    poses = [nerf.pose_spherical(a, -30.0, 4.0) for a in (-40.0, 75.0)]
-    cache = {}
-
-    def frame(i, chunk=100, **over):
-        """One frame's maps; the dense ones (no occupancy, the package's own query function) are cached."""
-        key = (i, chunk, tuple(sorted(over.items()))) if "occupancy" not in over and "network_query_fn" not in over else None
-        if key in cache:
-            return cache[key]
-        with torch.no_grad():
-            rgb, depth, acc, ex = nerf.render(H, W, K, chunk=chunk, c2w=poses[i][:3, :4].to(gpu), retraw=True,
-                                              **dict(kw, **over))
-        out = dict(ex, rgb=rgb, depth=depth, acc=acc)
-        if key is not None:
-            cache[key] = out
-        return out
-
-    return dict(lo=lo, hi=hi, bbox=bbox, kw=kw, emb=emb, frame=frame, K=K, poses=poses)
+    s = build_scene(nerf, gpu)
+    s["frame"] = functools.partial(s["frame"], chunk=100)
+    return s
 
 
 def masked_query_fn(scene, grid):
@@ -106,16 +42,6 @@ def masked_query_fn(scene, grid):
     def wrapped(pts, viewdirs, fn):
         return nqf(pts, viewdirs, fn) * grid.query(pts)[..., None]
     return wrapped
-
-
-def assert_maps_equal(got, ref, what, raw_plus_zero=False):
-    for k in MAPS:
-        if k not in ref:
-            continue
-        a, b = got[k], ref[k]
-        if k == "raw" and raw_plus_zero:
-            a, b = a + 0.0, b + 0.0     # -0.0 (negative x 0 in the reference) -> +0.0, nothing else changes
-        assert bits_equal(a, b), f"{what}: {k} differs in {int((a != b).sum())} values"
 
 
 # ---------------------------------------------------------------- 1. cell rule
@@ -275,54 +201,14 @@ def test_trained_scene_psnr_within_0p1_db(nerf, gpu, golden):
     """The two-sphere scene of test_gpu_converge.py, 300 iterations, a grid with the defaults: PSNR of the
     held-out and the novel rays against the procedural targets within 0.1 dB of the dense render (the
     project's parity bar)."""
-    g = golden("f19_converge")
-    c = ast.literal_eval(str(g["config"]))
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    emb = nerf.HashEmbedder(bbox, finest_resolution=1024).to(gpu)
-    table = closed_form_table(scale=c["table_scale"], salt=c["table_salt"])
-
-    def net(prefix):
-        m = nerf.NeRFSmall(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-                           input_ch=32, input_ch_views=16).to(gpu)
-        with torch.no_grad():
-            for k, p in m.named_parameters():
-                p.copy_(torch.from_numpy(g[prefix + k.replace(".", "_")]))
-        return m
-
-    coarse, fine = net("coarse0_"), net("fine0_")
-    with torch.no_grad():
-        for i, e in enumerate(emb.embeddings):
-            e.weight.copy_(torch.from_numpy(table[i]))
-    sh = nerf.SHEncoder()
-    nqf = lambda inputs, viewdirs, fn: nerf.run_network(inputs, viewdirs, fn, emb, sh)  # noqa: E731
-    kw = dict(network_query_fn=nqf, perturb=1.0, N_importance=128, network_fine=fine, N_samples=64,
-              network_fn=coarse, embed_fn=emb, use_viewdirs=True, white_bkgd=True, raw_noise_std=0.0,
-              predict_normals=False, ndc=False, lindisp=False, near=2.0, far=6.0, pytest=True)
-    kw_test = dict(kw, perturb=0.0, pytest=False)
-    args = nerf.make_args(lrate=c["lrate"], lrate_decay=c["lrate_decay"], sparse_loss_weight=c["sparsity"],
-                          tv_loss_weight=0.0, N_samples=64, N_importance=128, white_bkgd=True)
-    (ro, rd, rgb), ev, nv = convergence_rays()
-    ro, rd, rgb = (torch.from_numpy(a).to(gpu) for a in (ro, rd, rgb))
-    opt = nerf.RAdam([{"params": list(coarse.parameters()) + list(fine.parameters()), "weight_decay": 1e-6},
-                      {"params": list(emb.parameters()), "eps": 1e-15}], lr=c["lrate"], betas=(0.9, 0.99))
-    def psnr_of(o, d, target, **over):
-        with torch.no_grad():
-            out, _, _, _ = nerf.render(800, 800, None, rays=(o, d), **dict(kw_test, **over))
-            return (-10.0 * torch.log10(((out - target) ** 2).mean())).item()
-
-    ev, nv = ([torch.from_numpy(a).to(gpu) for a in part] for part in (ev, nv))
-    before = psnr_of(*ev)
-    rng = np.random.RandomState(100)
-    for it in range(1, 301):
-        idx = torch.from_numpy(rng.choice(ro.shape[0], c["R"], replace=False).astype(np.int64)).to(gpu)
-        nerf.train_step((ro[idx], rd[idx]), rgb[idx], kw, opt, args, it)
-    for m in (coarse, fine, emb):
-        m.eval()
-    grid = nerf.OccupancyGrid(bbox, device=gpu).update(emb, [coarse, fine])
+    ts = two_sphere_scene(nerf, gpu, golden("f19_converge"))
+    psnr_of = lambda *rays, **over: ts.psnr_of(*rays, **over)[0]  # noqa: E731
+    before = psnr_of(*ts.ev)
+    ts.train(300)
+    grid = nerf.OccupancyGrid(ts.bbox, device=gpu).update(ts.emb, [ts.coarse, ts.fine])
     print(f"occupied fraction {grid.occupied_fraction():.4f} of {grid.resolution}^3 cells")
 
-    for name, (o, d, t) in (("held-out", ev), ("novel", nv)):
+    for name, (o, d, t) in (("held-out", ts.ev), ("novel", ts.nv)):
         dense = psnr_of(o, d, t)
         sparse = psnr_of(o, d, t, occupancy=grid)
         n, P = grid.last_counts()       # the fine pass of the last chunk

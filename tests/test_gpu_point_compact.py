@@ -1,7 +1,7 @@
 """The point compaction of the forward-only render paths (csrc/sparse_points.hip over csrc/compact_common.h):
 nerf_occ_compact and nerf_ert_compact called directly, against NumPy, needs an MI355X.
 
-The cell rule, the masks and the early-stop entry's driver are those of test_gpu_early_stop.py. Points are
+The cell rule, the masks and the drivers of the two entries are those of forward_only.py. Points are
 uniform in the scene box scaled by 1.3 about its centre (45 % inside), the grid is the half-full random mask
 at resolution 5, alive flags are set with probability 0.6: every case keeps between 5 % and 95 % of its
 candidates, which each test asserts on the CPU before anything runs on the GPU (sizes below 64 excepted).
@@ -13,8 +13,8 @@ import numpy as np
 import pytest
 import torch
 
+from forward_only import bits_equal, np_cells, random_mask, run_compact, run_occ_compact
 from tables import blender_bbox
-from test_gpu_early_stop import bits_equal, np_cells, random_mask, run_compact
 
 pytestmark = pytest.mark.gpu
 
@@ -45,27 +45,6 @@ def random_grid(nerf, gpu, h):
     grid = nerf.OccupancyGrid((torch.from_numpy(h["lo"]), torch.from_numpy(h["hi"])), resolution=RES, device=gpu)
     grid.set_mask(random_mask(RES))
     return grid
-
-
-def run_occ_compact(L, gpu, pts, samples_per_ray, sh_rays, viewdirs, lo, hi, grid, raw):
-    """nerf_occ_compact as OccupancyGrid.compact drives it: count, one host read, scatter."""
-    i32, f = dict(device=gpu, dtype=torch.int32), dict(device=gpu, dtype=torch.float32)
-    P = pts.shape[0]
-    count = torch.full((1,), -1, **i32)
-    ws = torch.empty(int(L.load().nerf_occ_compact_workspace_bytes(P)) // 4, **i32)
-    bmin, bmax = L.host_f32(lo), L.host_f32(hi)
-
-    def run(stages, cap, rows, pts_c, sh_c):
-        L.call("nerf_occ_compact", L.ptr(pts), P, L.ptr(sh_rays, "sh", allow_none=True),
-               L.ptr(viewdirs, "dirs", allow_none=True), samples_per_ray, bmin, bmax, grid.resolution, grid._bits(),
-               stages, cap, L.ptr(rows, "rows", torch.int32, True), L.ptr(count, "count", torch.int32),
-               L.ptr(pts_c, "pts_c", allow_none=True), L.ptr(sh_c, "sh_c", allow_none=True), L.ptr(raw),
-               L.ptr(ws, "ws", torch.int32), ws.numel() * 4, L.stream())
-    run(1, 0, None, None, None)
-    k = int(count.item())
-    rows, pts_c, sh_c = torch.empty(k, **i32), torch.empty(k, 3, **f), torch.empty(k, 16, **f)
-    run(2, k, rows if k else None, pts_c if k else None, sh_c if k else None)
-    return rows, pts_c, sh_c
 
 
 def check_outputs(got, raw, h, kept, cand, samples_per_ray, want_sh_rows, what):

@@ -1,8 +1,7 @@
 """Per-ray sample bounds from the occupancy grid (csrc/ray_span.hip, render(ray_bounds=grid)),
 needs an MI355X.
 
-Scene of test_gpu_occupancy.py (blender_bbox, tables uniform +-0.05, finest_res 512, white background, eval
-mode, perturb = 0), two 12 x 16 frames from (-40 deg, 75 deg) at -30 deg, radius 4, near = 0.5, far = 9.0.
+The scene of forward_only.py (build_scene; perturb = 0).
 
 The span kernel is held to three things: it is the same bits as np_span below (its rule restated in NumPy
 fp32, vectorised over the rays), it is conservative against the cell rule applied to fp32 sample positions
@@ -13,54 +12,13 @@ import numpy as np
 import pytest
 import torch
 
-from tables import blender_bbox
+from forward_only import (FAR, H, NEAR, W, ball_mask, bits_equal, build_scene, make_mask, np_query, random_mask,
+                          scatter_back)
 
 pytestmark = pytest.mark.gpu
 
-H, W = 12, 16
-NEAR, FAR = 0.5, 9.0
 f32 = np.float32
 PAD_SCALE = f32(0.0625)      # pad = 2^-4 min_a cell_a / |d_a| (csrc/ray_span.hip)
-
-
-# ---------------------------------------------------------------- the cell rule and the masks (test_gpu_occupancy.py)
-def np_cells(pts, lo, hi, res):
-    """The cell rule of csrc/occupancy.hip in NumPy fp32: (linear cell id, inside the box)."""
-    pts, lo, hi = (np.asarray(a, np.float32) for a in (pts, lo, hi))
-    cell = ((hi - lo) / np.float32(res)).astype(np.float32)
-    xc = np.minimum(np.maximum(pts, lo), hi)
-    base = np.floor((xc - lo) / cell).astype(np.int64)
-    idx = np.minimum(base, res - 1)
-    inside = (pts == np.maximum(np.minimum(pts, hi), lo)).all(-1)
-    return (idx[..., 0] * res + idx[..., 1]) * res + idx[..., 2], inside
-
-
-def np_query(pts, lo, hi, mask):
-    cid, inside = np_cells(pts, lo, hi, mask.shape[0])
-    return inside & mask.reshape(-1)[cid]
-
-
-def random_mask(res):
-    return np.random.default_rng(res).random((res, res, res)) < 0.5
-
-
-def ball_mask(res=16, radius=0.35):
-    c = (np.arange(res) + 0.5) / res * 2.0 - 1.0
-    x, y, z = np.meshgrid(c, c, c, indexing="ij")
-    return np.sqrt(x * x + y * y + z * z) <= radius
-
-
-def make_mask(name, res):
-    if name == "random":
-        return random_mask(res)
-    if name == "ball":
-        return ball_mask(res)
-    return np.full((res, res, res), name == "full")
-
-
-def bits_equal(a, b):
-    a, b = a.contiguous(), b.contiguous()
-    return a.shape == b.shape and a.dtype == b.dtype and torch.equal(a.view(torch.int32), b.view(torch.int32))
 
 
 # ---------------------------------------------------------------- the span rule in NumPy fp32
@@ -319,44 +277,11 @@ def random_rays(n, lo, hi, seed=5):
 
 @pytest.fixture(scope="module")
 def scene(nerf, gpu):
-    lo, hi = blender_bbox()
-    bbox = (torch.from_numpy(lo), torch.from_numpy(hi))
-    args = nerf.make_args(bounding_box=bbox, finest_res=512, N_samples=32, N_importance=32, white_bkgd=True)
-    torch.manual_seed(0)
-    _, kw, _, _, _ = nerf.create_nerf(args, device=gpu)
-    kw.update(near=NEAR, far=FAR)
-    emb = kw["embed_fn"]
-    with torch.no_grad():
-        g = torch.Generator().manual_seed(3)
-        for e in emb.embeddings:
-            e.weight.copy_((torch.rand(e.weight.shape, generator=g) * 2 - 1) * 0.05)
-    for m in (kw["network_fn"], kw["network_fine"], emb):
-        m.eval()
-    focal = 0.5 * W / np.tan(0.5 * 0.6911112070083618)
-    K = np.array([[focal, 0, 0.5 * W], [0, focal, 0.5 * H], [0, 0, 1]])
-    poses = [nerf.pose_spherical(a, -30.0, 4.0) for a in (-40.0, 75.0)]
-    from indoor_nerf_amd.render import _pack_rays as pack
-
-    def packed(i):
-        """The packed rows [H * W, 11] of frame i, as render() builds them."""
-        ro, rd = nerf.get_rays(H, W, K, poses[i][:3, :4].to(gpu))
-        return pack(H, W, K, ro, rd, kw["near"], kw["far"], kw["ndc"], kw["use_viewdirs"])
-
-    def grid_of(mask):
-        grid = nerf.OccupancyGrid(bbox, resolution=mask.shape[0], device=gpu)
-        grid.set_mask(mask)
-        return grid
-
-    def frame(i, chunk=4096, **over):
-        with torch.no_grad():
-            rgb, depth, acc, ex = nerf.render(H, W, K, chunk=chunk, c2w=poses[i][:3, :4].to(gpu), retraw=True,
-                                              **dict(kw, **over))
-        return dict(ex, rgb_map=rgb, depth_map=depth, acc_map=acc)
-
+    sc = build_scene(nerf, gpu)
+    lo, hi, packed = sc["lo"], sc["hi"], sc["packed"]
     frame_rays = np.concatenate([packed(i).cpu().numpy()[:, :8] for i in (0, 1)])
     pool = np.concatenate([special_rays(lo, hi), frame_rays, random_rays(4097, lo, hi)])[:4097]
-    return dict(lo=lo, hi=hi, bbox=bbox, kw=kw, K=K, poses=poses, packed=packed, grid_of=grid_of, frame=frame,
-                pool=pool, n_special=len(special_rays(lo, hi)), cache={})
+    return dict(sc, pool=pool, n_special=len(special_rays(lo, hi)))
 
 
 def gpu_span(scene, gpu, rays, mask, cols=8):
@@ -524,9 +449,6 @@ def test_span_is_tight(nerf, gpu, scene, res, name):
 
 
 # ---------------------------------------------------------------- 4. render(ray_bounds=) = the hand composition
-FILL = {"rgb_map": 1.0, "rgb0": 1.0, "depth_map": float("nan"), "depth0": float("nan")}    # white background
-
-
 def hand_composition(nerf, scene, i, grid, chunk, **over):
     """The same thing from existing pieces: pack, ray_span, torch indexing, batchify_rays, scatter."""
     kw = dict(scene["kw"], **over)
@@ -538,11 +460,7 @@ def hand_composition(nerf, scene, i, grid, chunk, **over):
         kw.pop(k)
     with torch.no_grad():
         part = nerf.batchify_rays(sel, chunk, retraw=True, **kw)
-    out = {}
-    for k, v in part.items():
-        full = torch.full((H * W,) + tuple(v.shape[1:]), FILL.get(k, 0), device=v.device, dtype=v.dtype)
-        full[hit] = v
-        out[k] = full.reshape((H, W) + tuple(v.shape[1:]))
+    out = scatter_back(part, hit)
     out.update(ray_hit=hit.reshape(H, W), ray_span=span.reshape(H, W, 2))
     return out
 

@@ -16,6 +16,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import render_time as rt  # noqa: E402
+from tables import convergence_rays  # noqa: E402  (render_time puts tests/golden on sys.path)
 
 nerf = rt.nerf
 
@@ -27,7 +28,7 @@ def main():
     a = ap.parse_args()
     bbox, emb, coarse, fine, kw = rt.trained_scene(a.iters)
     gpu = torch.device("cuda:0")
-    _, ev, nv = rt.convergence_rays()
+    _, ev, nv = convergence_rays()
     sets = {"eval": [torch.from_numpy(x).to(gpu) for x in ev], "novel": [torch.from_numpy(x).to(gpu) for x in nv]}
 
     def psnr(o, d, t, **over):
