@@ -231,6 +231,8 @@ int nerf_sh4_fwd(const float* d_dirs, int64_t n, float* d_out /* [n,16] */, void
  * the MLP kernels use as the pre-split matrix operand (16-B aligned; the point order's two segments
  * as for d_viewdirs), i.e. nerf_sample_stratified_sh's d_sh.
  * d_keep may be NULL (keep all). Output d_raw [P,4] = [rgb_raw(3), sigma_raw].
+ * nerf_mlp_fwd_bf16 (below) is the same forward with one bf16 piece per operand, for forward-only
+ * rendering: it reads piece 0 of the per-ray records and converts the other two view encodings itself.
  */
 typedef struct {
     const float* w0;
@@ -311,6 +313,19 @@ int nerf_mlp_fwd_ord(const float* d_feat, int64_t feat_stride_point, int64_t fea
                      const nerf_mlp_weights* weights, float* d_raw, float* d_geo,
                      const float* d_act_qrec, uint32_t* d_act_minmax, int64_t act_calib_points,
                      const nerf_point_order* order, void* stream);
+/* Forward-only rendering (additive, ABI 12): nerf_mlp_fwd_ord's forward with ONE bf16 piece
+ * per operand instead of the fp32-accurate three. W0, W1, C0 and C1, the hash features, the SH coefficients
+ * (all three view modes) and each hidden activation that feeds a layer are rounded to bf16 once (round to
+ * nearest even); products are exact, sums fp32; the output layer C2 is exact fp32 on the unrounded hidden
+ * layer and raw[:, 3] is the unrounded fp32 sigma (0 where d_keep is 0). 20 MFMAs per 32-point tile instead
+ * of 112. No geo output, no A-CAQ record, no calibration launch, no saved h3: there is no backward for it.
+ * A point's result does not depend on the other points of the launch. */
+int nerf_mlp_fwd_bf16(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                      const float* d_sh, int64_t sh_stride,
+                      const float* d_viewdirs, int64_t samples_per_ray,
+                      const uint8_t* d_keep, int64_t n_points,
+                      const nerf_mlp_weights* weights, float* d_raw,
+                      const nerf_point_order* order, void* stream);
 int nerf_mlp_bwd_q(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
                    const float* d_sh, int64_t sh_stride,
                    const float* d_viewdirs, int64_t samples_per_ray,

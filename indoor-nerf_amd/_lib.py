@@ -165,6 +165,8 @@ SIGNATURES = {
                        c_vp, c_vp, c_vp, c_vp, c_i64, c_vp],
     "nerf_mlp_fwd_ord": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
                          c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(PointOrder), c_vp],
+    "nerf_mlp_fwd_bf16": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
+                          c_vp, ctypes.POINTER(PointOrder), c_vp],
     "nerf_mlp_fwd_h3": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
                         c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(PointOrder), c_vp, c_vp],
     "nerf_mlp_bwd_q": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),

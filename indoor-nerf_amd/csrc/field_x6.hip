@@ -1378,6 +1378,162 @@ int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_
     return NERF_OK;
 }
 
+// ================================================================ bf16 forward (forward-only rendering)
+// mlp_fwd_x6_kernel<false>'s forward with ONE bf16 piece per operand: every weight of
+// W0, W1, C0', C1, every hash feature, every SH coefficient and every hidden activation that feeds a
+// layer is rounded to bf16 once (round to nearest even, v_cvt_pk_bf16_f32), a product is one
+// v_mfma_f32_32x32x16_bf16 and every sum is fp32. 20 MFMAs per 32-point tile (W0 4, W1 4, C0 4, C1 8)
+// instead of 112, one conversion per pair of values instead of split2's 11 VALU ops, and a 22 KB weight
+// image (piece 0 of the x6 image) instead of 66.8 KB. The output layer stays rgb_c2 (exact fp32 FMAs on
+// the unrounded h3) and sigma is the unrounded fp32 accumulator o[0]. Same tile orientation, loaders,
+// point order and epilogue as the x6 kernel; no A-CAQ record, no geo output, no saved h3.
+
+// Piece 0 of fill_images' image (the C2 rows are kept: rows 3..15 are W1's zero rows below)
+__device__ inline void fill_image_bf16(__bf16* img, const nerf_mlp_weights& W) {
+    for (int base = threadIdx.x; base < L_END; base += kFillRound * blockDim.x) {
+        float v[kFillRound];
+#pragma unroll
+        for (int u = 0; u < kFillRound; ++u) {
+            const int idx = base + u * (int)blockDim.x;
+            v[u] = idx < L_END ? image_value(idx, W) : 0.f;
+        }
+#pragma unroll
+        for (int u = 0; u < kFillRound; ++u) {
+            const int idx = base + u * (int)blockDim.x;
+            if (idx >= L_END) continue;
+            int off;
+            if (idx < L_W1) off = IM_W0 + (idx >> 5) * S32 + (idx & 31);
+            else if (idx < L_C0) { const int k = idx - L_W1; off = IM_W1 + (k >> 6) * S64 + (k & 63); }
+            else if (idx < L_C1) { const int k = idx - L_C0; off = IM_C0 + (k >> 5) * S32 + (k & 31); }
+            else if (idx < L_C2) { const int k = idx - L_C1; off = IM_C1 + (k >> 6) * S64 + (k & 63); }
+            else { const int k = idx - L_C2; off = IM_C2 + (k >> 6) * S64 + (k & 63); }
+            img[off] = (__bf16)v[u];
+        }
+    }
+}
+
+// 8 values of an operand fragment rounded to bf16 (element i = half (i & 1) of dword i >> 1)
+__device__ __forceinline__ u32x4 pack8(float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7) {
+    return u32x4{pk_bf16(v0, v1), pk_bf16(v2, v3), pk_bf16(v4, v5), pk_bf16(v6, v7)};
+}
+
+// chunk c of a 32-row accumulator tile (registers 8c .. 8c+7) as the next layer's B operand
+__device__ __forceinline__ u32x4 pack_chunk(const floatx16& v, int c) {
+    return pack8(v[8 * c], v[8 * c + 1], v[8 * c + 2], v[8 * c + 3], v[8 * c + 4], v[8 * c + 5], v[8 * c + 6],
+                 v[8 * c + 7]);
+}
+
+__device__ __forceinline__ u32x4 pack_arr(const float* v) {
+    return pack8(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7]);
+}
+
+// row_read of the one-piece image
+__device__ __forceinline__ u32x4 row_read1(const __bf16* img, int base, int S, int r, int col0) {
+    return row_read_pair(img, base + r * S, base + r * S, 0, col0);
+}
+
+// The C0 operand of the point's SH, bf16_rne(sh) in every view mode: piece 0 of the per-ray record
+// (exactly that), else the per-point row / the evaluated SH4 converted here
+__device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, bool valid, int h) {
+    if (!a.viewdirs && a.sh_stride == 0) {
+        const uint32_t pc = valid ? pt : (uint32_t)(a.P - 1);
+        const uint16_t* rec = reinterpret_cast<const uint16_t*>(a.sh + ray_of(a, pc) * (uint32_t)kShRecord) + 32;
+        const u32x2 g0 = *reinterpret_cast<const u32x2*>(rec + 4 * h);
+        const u32x2 g1 = *reinterpret_cast<const u32x2*>(rec + 8 + 4 * h);
+        return u32x4{g0.x, g0.y, g1.x, g1.y};   // tail lanes: the last point's (load_x6)
+    }
+    float shv[8];
+    load_sh6(a, pt, valid, h, shv, 0);
+    return pack_arr(shv);
+}
+
+// 512-thread blocks on the x6 forward's grid: at most two blocks per CU, 4 waves per SIMD. The chain needs 78
+// registers and no scratch, and the 22.3 KB image would allow more, but a tile's time is its ~425 VALU and
+// 20 MFMA issue slots, not latency: loading the next tile's inputs under the current chain (112 registers)
+// measured 37.7 us against 35.8 us per 786,432 points without it.
+__global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
+    __shared__ __attribute__((aligned(16))) __bf16 img[IM_PIECE];
+    __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
+    fill_image_bf16(img, a.W);
+    fill_c2f(c2f, a.W);
+    __syncthreads();
+    const int lane = threadIdx.x & 63, j = lane & 31, m = j, h = lane >> 5;
+    const int64_t n_tiles = (a.P + 31) / 32;
+    const int wpb = blockDim.x >> 6;
+    for (int64_t tile = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * wpb) {
+        const uint32_t pt = (uint32_t)(tile * 32 + j);
+        const bool valid = tile * 32 + j < a.P;
+        float x[16];
+        load_x6(a, pt, valid, h, x, 0);
+        const u32x4 SH = load_sh_bf16(a, pt, valid, h);
+        const int z = opaque_zero();
+        const __bf16* im = img + z;
+        // layer 0: h1 = relu(W0 x)
+        floatx16 h1[2];
+        h1[0] = h1[1] = zero16();
+        {
+            const u32x4 xb[2] = {pack_arr(x), pack_arr(x + 8)};
+#pragma unroll
+            for (int c = 0; c < 2; ++c)
+#pragma unroll
+                for (int t = 0; t < 2; ++t)
+                    h1[t] = X6_MFMA(row_read1(im, IM_W0, S32, 32 * t + m, 16 * c + 4 * h), xb[c], h1[t]);
+        }
+        relu16i(h1[0]); relu16i(h1[1]);
+        // L1: o = W1 h1 on the 32-row tile: rows 16..31 read a zero row of C2's padding (rows 3..15)
+        floatx16 o = zero16();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const u32x4 A = row_read_pair(im, IM_W1 + (m & 15) * S64, IM_C2 + 8 * S64, m, 32 * t + 16 * c + 4 * h);
+                o = X6_MFMA(A, pack_chunk(h1[t], c), o);
+            }
+        // C0: h2 = relu(C0' [o rows 0..15 ; sh])
+        floatx16 h2[2];
+        h2[0] = h2[1] = zero16();
+        {
+            const u32x4 O0 = pack_chunk(o, 0);
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                h2[t] = X6_MFMA(row_read1(im, IM_C0, S32, 32 * t + m, 4 * h), O0, h2[t]);
+                h2[t] = X6_MFMA(row_read1(im, IM_C0, S32, 32 * t + m, 16 + 4 * h), SH, h2[t]);
+            }
+        }
+        relu16i(h2[0]); relu16i(h2[1]);
+        // C1: h3 = relu(C1 h2)
+        floatx16 h3[2];
+        h3[0] = h3[1] = zero16();
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int c = 0; c < 2; ++c) {
+                const u32x4 hb = pack_chunk(h2[t], c);
+#pragma unroll
+                for (int to = 0; to < 2; ++to)
+                    h3[to] = X6_MFMA(row_read1(im, IM_C1, S64, 32 * to + m, 32 * t + 16 * c + 4 * h), hb, h3[to]);
+            }
+        relu16i(h3[0]); relu16i(h3[1]);
+        float rgb[3];
+        rgb_c2(c2f + z, h3, h, rgb);
+        if (h == 0 && valid) {
+            const bool keep = a.keep ? a.keep[pt] != 0 : true;
+            *reinterpret_cast<float4*>(a.raw + 4u * io_row(a, pt)) = make_float4(rgb[0], rgb[1], rgb[2], keep ? o[0] : 0.f);
+        }
+    }
+}
+
+int launch_mlp_fwd_bf16(const MlpArgs& a, hipStream_t stream) {
+    NERF_REQUIRE(fits_u32(a), "mlp_fwd_bf16: %lld points exceed 32-bit indexing", (long long)a.P);
+    NERF_REQUIRE(!a.aq && !a.act_minmax && !a.geo_out && !a.h3,
+                 "mlp_fwd_bf16: no A-CAQ record, geo output or saved h3 (forward-only rendering)");
+    const int64_t tiles = (a.P + 31) / 32;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
+    hipLaunchKernelGGL(mlp_fwd_bf16_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    NERF_CHECK_LAUNCH("mlp_fwd_bf16");
+    return NERF_OK;
+}
+
 #ifdef NERF_X6CG_PROF
 // diagnostic builds only: the chain / wgrad waves' wait and loop cycles summed over all waves since
 // the last call (s_memtime units), then the chain wave's waits per stage; all reset

@@ -190,6 +190,7 @@ class FieldFn(torch.autograd.Function):
             raise NotImplementedError("run_network: gradients w.r.t. positions/directions are not implemented")
         n_tab = embedder.n_levels
         tables, weights, head = params[:n_tab], params[n_tab:n_tab + 5], params[n_tab + 5:]
+        bf16 = getattr(pts, "_nerf_mlp", None) is not None   # run_network's checked MlpRequest
         pts = pts.contiguous()
         sh_rays = getattr(viewdirs, "_nerf_sh", None)   # render_rays' per-ray SH4 rows (sh_stride 0)
         viewdirs = viewdirs.contiguous()
@@ -240,9 +241,13 @@ class FieldFn(torch.autograd.Function):
         if (_SAVE_H3["on"] and arec is None and not _ACTIVE["on"] and P > 0
                 and any(ctx.needs_input_grad[7:7 + n_tab + 5])):
             h3 = torch.empty(int(_lib.load().nerf_mlp_h3_bytes(P)) // 4, device=dev, dtype=torch.float32)
-        _lib.call("nerf_mlp_fwd_h3", *feat_args, P, _weights_struct(weights, w0q), _lib.ptr(raw, "raw"),
-                  _lib.ptr(o16, "geo", allow_none=True), _lib.ptr(arec, "act_record", allow_none=True), None, 0,
-                  _point_order(order), _lib.ptr(h3, "h3", allow_none=True), _lib.stream())
+        if bf16:   # forward-only: no head, no quantizers, no gradients (sparse_field.check_mlp_field)
+            _lib.call("nerf_mlp_fwd_bf16", *feat_args, P, _weights_struct(weights), _lib.ptr(raw, "raw"),
+                      _point_order(order), _lib.stream())
+        else:
+            _lib.call("nerf_mlp_fwd_h3", *feat_args, P, _weights_struct(weights, w0q), _lib.ptr(raw, "raw"),
+                      _lib.ptr(o16, "geo", allow_none=True), _lib.ptr(arec, "act_record", allow_none=True), None, 0,
+                      _point_order(order), _lib.ptr(h3, "h3", allow_none=True), _lib.stream())
         ctx.h3 = h3
         if head and order is not None:   # keep scattered to the merged rows by the head's own launch
             raw, keep = _head_forward(o16, raw, keep, head, rows=order[0])
@@ -648,19 +653,29 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
     """run_nerf.py:53-68. inputs [..., S, 3], viewdirs [R, 3]. Fused when the modules are ours;
     netchunk is then only a memory knob the fused kernels do not need."""
     sparse = getattr(inputs, "_nerf_sparse", None)   # sparse_field.SparseRequest of this render_rays call
+    mlp = getattr(inputs, "_nerf_mlp", None)         # sparse_field.MlpRequest of it (mlp_precision="bf16")
+    if mlp is not None:
+        mlp.used = True
     if sparse is not None:
         from .sparse_field import run_network_sparse
         sparse.used = True
-        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse)
-    fused = (isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall)
-             and isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3)
+        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse, mlp)
+    call_ok = isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3
+    if mlp is not None:   # never the eager path below, and never fp32 silently
+        from .sparse_field import check_mlp_field
+        check_mlp_field(call_ok, "inputs [R, S, 3]", fn, embed_fn)
+    fused = isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall) and call_ok
     if fused:
         if embed_fn.training:
             embed_fn.current_step += 1
         R, S = inputs.shape[0], inputs.shape[1]
         reuse = getattr(inputs, "_nerf_reuse", None)     # render.CoarseReuse of this render_rays call
-        raw = FieldFn.apply(inputs.reshape(-1, 3), viewdirs, S, embed_fn, fn, netchunk, reuse,
-                            *embed_fn.tables(), *fn.field_params())
+        flat = inputs.reshape(-1, 3)
+        if mlp is not None:
+            flat._nerf_mlp = mlp
+        raw = FieldFn.apply(flat, viewdirs, S, embed_fn, fn, netchunk, reuse, *embed_fn.tables(), *fn.field_params())
+        if mlp is not None:
+            del flat._nerf_mlp
         out = raw.reshape(R, S, fn.raw_channels)
         # without a normals head FieldFn's backward only queues its job: raw2outputs may then defer the
         # compositing backward too (render.CompositeJob)

@@ -374,14 +374,27 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return out
 
 
-def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None):
+def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16):
+    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16")."""
+    if not bf16:
+        return network_query_fn(pts, viewdirs, fn)
+    from .sparse_field import MlpRequest
+    req = pts._nerf_mlp = MlpRequest()
+    raw = network_query_fn(pts, viewdirs, fn)
+    del pts._nerf_mlp
+    if not req.used:   # a foreign query function ignores the attribute: never render in fp32 silently
+        raise ValueError("render_rays: mlp_precision needs a network_query_fn that calls this package's run_network")
+    return raw
+
+
+def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False):
     """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
     (stops int32 [R], early_stop.py), None otherwise (stops None)."""
     if occupancy is None and early is None:
-        return network_query_fn(pts, viewdirs, fn), None
+        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16), None
     from .sparse_field import SparseRequest
     req = pts._nerf_sparse = SparseRequest(occupancy, early)
-    raw = network_query_fn(pts, viewdirs, fn)
+    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16)
     del pts._nerf_sparse
     if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
         raise ValueError(f"render_rays: {req.what} needs a network_query_fn that calls this package's run_network")
@@ -398,7 +411,7 @@ def last_early_stop_counts():
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False, lindisp=False,
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
-                march=None, march_samples=512, march_points=1 << 21):
+                march=None, march_samples=512, march_points=1 << 21, mlp_precision=None):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -415,12 +428,23 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     list. The result is what masking sigma by grid.query in that dense render gives: rgb_map, depth_map,
     acc_map, march_samples (int32 [R], the kept samples per ray) and rays_d; with retraw also the packed
     raw [n, 4], pts [n, 3], z_vals [n] and march_offsets (int32 [R + 1]). N_samples and N_importance are not
-    used. None (the default) leaves the call as it is without it."""
+    used. None (the default) leaves the call as it is without it.
+    mlp_precision (None, "fp32" or "bf16"; forward-only rendering): "bf16" runs every MLP forward
+    of the call with one bf16 piece per operand and fp32 sums (nerf_mlp_fwd_bf16) instead of the fp32-accurate
+    kernel: weights, hash features, SH and hidden activations are rounded to bf16, sigma and the colour layer's
+    sums stay fp32. Composes with occupancy=, early_stop= and march=. None and "fp32" are the call without it."""
+    bf16 = False
+    if mlp_precision is not None:
+        from .sparse_field import check_mlp_nets, check_mlp_precision
+        bf16 = check_mlp_precision(mlp_precision, "render_rays")
+    if bf16:
+        check_mlp_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn, predict_normals)
     if march is not None:
         return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points,
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
-                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop)
+                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
+                                  bf16=bf16)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -459,7 +483,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
     raw, stops = _query(network_query_fn, pts, viewdirs, network_fn, occupancy,
-                        None if early is None else (z, rays_d) + early)
+                        None if early is None else (z, rays_d) + early, bf16)
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -501,7 +525,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
             pts._nerf_reuse = reuse
         stops0 = stops
         raw, stops = _query(network_query_fn, pts, viewdirs, run_fn, occupancy,
-                            None if early is None else (z, rays_d) + early)
+                            None if early is None else (z, rays_d) + early, bf16)
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()
@@ -562,7 +586,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None):
+                       predict_normals=False, occupancy=None, early_stop=None, bf16=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing."""
     run_fn = network_fn if network_fine is None else network_fine
@@ -578,7 +602,7 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     f = dict(device=dev, dtype=torch.float32)
     if n > 0:
         req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
-        raw = network_query_fn(pts_c, rays[:, 8:11], run_fn)
+        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16)
         del pts_c._nerf_sparse
         if not req.used:   # a foreign query function ignores the attribute: never fall back silently
             raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
@@ -755,13 +779,16 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     ray_hit (bool) and ray_span ([near', far'] per ray). Composes with occupancy= and early_stop=. None (the
     default) leaves the call as it is without it.
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
-    spans its own [near', far']. retraw is refused with march: the packed entries of several chunks do not
-    concatenate."""
+    spans its own [near', far']. mlp_precision goes to render_rays as well. retraw is refused with
+    march: the packed entries of several chunks do not concatenate."""
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")
     if ray_bounds is not None:
         _check_ray_bounds(ray_bounds)
+    if kwargs.get("mlp_precision") is not None:   # also when no chunk reaches render_rays (ray_bounds with every ray missed)
+        from .sparse_field import check_mlp_precision
+        check_mlp_precision(kwargs["mlp_precision"], "render")
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, K, c2w)
     else:

@@ -16,7 +16,8 @@ from .occupancy import _check_modules
 
 # why each keyword is forward-only (check_forward_only's and _begin_field_call's refusals)
 NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training",
-                   "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training"}
+                   "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training",
+                   "mlp_precision": "the backward recomputes the forward in fp32"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -45,6 +46,61 @@ class MarchRequest:
     def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS):
         self.sh_c, self.max_points = sh_c, check_march_points(max_points)
         self.used = False
+
+
+class MlpRequest:
+    """render_rays' request of the bf16 MLP forward (mlp_precision="bf16"), attached to the point
+    tensor of every pass as `pts._nerf_mlp`, beside a SparseRequest / MarchRequest when there is one. run_network
+    sets `used` (a foreign query function leaves it False and render_rays raises) and routes every MLP forward
+    launch of the call to nerf_mlp_fwd_bf16."""
+    what = "mlp_precision"
+
+    def __init__(self):
+        self.used = False
+
+
+def check_mlp_precision(value, prefix):
+    """mlp_precision of `prefix` (render_rays, render) -> whether it asks for the bf16 forward; its refusals: an
+    unknown value, gradients enabled. Raw noise is fine: it is added after the field."""
+    if value is None or (isinstance(value, str) and value == "fp32"):
+        return False
+    if not (isinstance(value, str) and value == "bf16"):
+        raise ValueError(f"{prefix}: mlp_precision must be None, 'fp32' or 'bf16', got {value!r}")
+    check_forward_only("mlp_precision", prefix)
+    return True
+
+
+def check_mlp_nets(nets, embed_fn, predict_normals, prefix="render_rays"):
+    """render_rays' refusals with mlp_precision="bf16" that need its modules: before any launch, for the
+    networks of every pass."""
+    if predict_normals or any(getattr(fn, "raw_channels", 4) != 4 for fn in nets):
+        raise ValueError(f"{prefix}: mlp_precision does not support predict_normals or a normals head")
+    if embed_fn is not None:
+        for fn in nets:
+            _check_modules(embed_fn, fn, f"{prefix}: mlp_precision")
+
+
+def check_mlp_field(call_ok, shape_words, fn, embed_fn):
+    """The dense run_network's refusals for an MlpRequest, all before any launch (call_ok: SHEncoder view
+    encoding, viewdirs and the inputs that shape_words describes), in _begin_field_call's order."""
+    what = MlpRequest.what
+    if not call_ok:
+        raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
+    _check_modules(embed_fn, fn, what)
+    if fn.raw_channels != 4:
+        raise ValueError(f"{what}: a normals head is not supported (the bf16 forward has no geo output)")
+    if torch.is_grad_enabled():
+        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+
+
+def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order):
+    """The MLP launch of the sparse field calls: n points with level-major features (level stride sl) and SH rows
+    at stride 16 -> their rows of raw (order: a nerf_point_order or None); mlp: the call's MlpRequest or None."""
+    front = (feat, 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
+    if mlp is not None:
+        _lib.call("nerf_mlp_fwd_bf16", *front, order, _lib.stream())
+    else:
+        _lib.call("nerf_mlp_fwd_ord", *front, None, None, None, 0, order, _lib.stream())
 
 
 def check_march_points(m):
@@ -80,7 +136,7 @@ def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embe
         embed_fn.current_step += 1
 
 
-def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None):
     """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
     raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16) run over the list in
     slices of at most req.max_points points; a point's result does not depend on its slice."""
@@ -101,19 +157,18 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     for s0 in range(0, n, m):
         k = min(m, n - s0)
         embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * 2], 2, 2 * k, keep[:k])
-        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"), 16,
-                  None, 1, _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"),
-                  None, None, None, 0, None, _lib.stream())
+        mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
+                    _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None)
     return raw
 
 
-def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None):
     """run_network (field.py) for a SparseRequest: inputs [R, S, 3], viewdirs [R, 3] -> raw [R, S, 4] with
     the field evaluated at the kept samples only and zero rows elsewhere. Without early termination the call
     is one slab through req.grid.compact; with it, slabs of req.early's size front to back, nerf_ert_advance
     between them, and req.stop receives the stops."""
     if isinstance(req, MarchRequest):
-        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req)
+        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp)
     from .field import _point_order, _weights_struct
     what = req.what
     _begin_field_call(what, inputs.dim() == 3, "inputs [R, S, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
@@ -137,9 +192,8 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     def field(n, rows, pts_c, sh_c, feat, keep):
         """The field at the n compacted points; rows of raw `rows` receive the results."""
         embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep)
-        _lib.call("nerf_mlp_fwd_ord", _lib.ptr(feat, "feat"), 2, 2 * n, _lib.ptr(sh_c, "sh_c"), 16, None, 1,
-                  _lib.ptr(keep, "keep", torch.bool), n, weights, _lib.ptr(raw, "raw"),
-                  None, None, None, 0, _point_order((rows, 0, 0)), _lib.stream())
+        mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * n, _lib.ptr(sh_c, "sh_c"), _lib.ptr(keep, "keep", torch.bool), n,
+                    weights, _lib.ptr(raw, "raw"), _point_order((rows, 0, 0)))
 
     if req.early is None:
         # one slab, no alive flags: the grid's own compaction, every buffer sized exactly after the count

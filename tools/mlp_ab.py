@@ -2,7 +2,9 @@
 """Timing of the batched MLP backward (nerf_mlp_bwd_batch) on the lego step's two nets: the fine
 (4096 x 192 points) and the coarse (4096 x 64) net in one launch, HIP-event median per launch, plus a
 checksum of every output (dfeat of both nets, the ten weight gradients) so that builds can be told to
-compute the same thing. A/B of library builds: run once per build with NERF_HIP_LIB=<path>
+compute the same thing; and of the MLP forward at the step's two point counts (262,144 and 786,432), the
+fp32-accurate kernel (nerf_mlp_fwd) and the bf16 one (nerf_mlp_fwd_bf16) alternating, where the
+library has it. A/B of library builds: run once per build with NERF_HIP_LIB=<path>
 (tools/build_variant.py). JSON out."""
 import ctypes
 import json
@@ -41,6 +43,42 @@ def make_job(P, spr, seed, dev):
     j.weights, j.grads = w, gs
     j.graw, j.dfeat = _lib.ptr(graw), _lib.ptr(dfeat)
     return j, dict(feat=feat, vd=vd, keep=keep, graw=graw, dfeat=dfeat, ws=ws, grads=grads)
+
+
+def forward_ab(jobs, dev, rounds=5, per_round=20):
+    """Per point count: the x6 and the bf16 forward launch (view directions, keep flags, level-major features),
+    alternating launch by launch between device events after a warm-up of both: median and min in us, the ratio of
+    the medians, and the largest |raw difference| of the two kernels on the job's data."""
+    out = {}
+    if not hasattr(_lib.load(), "nerf_mlp_fwd_bf16"):
+        return out
+    for j, k, spr in jobs:
+        P = k["feat"].shape[1]
+        raws = {"x6": torch.empty(P, 4, device=dev), "bf16": torch.empty(P, 4, device=dev)}
+        front = (_lib.ptr(k["feat"]), 2, 2 * P, None, 0, _lib.ptr(k["vd"]), spr, _lib.ptr(k["keep"], dtype=torch.bool), P,
+                 ctypes.byref(j.weights))
+        fns = {"x6": lambda: _lib.call("nerf_mlp_fwd", *front, _lib.ptr(raws["x6"]), None, _lib.stream()),
+               "bf16": lambda: _lib.call("nerf_mlp_fwd_bf16", *front, _lib.ptr(raws["bf16"]), None, _lib.stream())}
+        ts = {name: [] for name in fns}
+        for _ in range(rounds):
+            for fn in fns.values():
+                for _ in range(3):
+                    fn()
+            torch.cuda.synchronize()
+            for _ in range(per_round):
+                for name, fn in fns.items():
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                    fn()
+                    e1.record()
+                    torch.cuda.synchronize()
+                    ts[name].append(e0.elapsed_time(e1))
+        row = {name + "_us_median": round(float(np.median(v)) * 1e3, 1) for name, v in ts.items()}
+        row.update({name + "_us_min": round(float(np.min(v)) * 1e3, 1) for name, v in ts.items()})
+        row["x6_over_bf16"] = round(float(np.median(ts["x6"]) / np.median(ts["bf16"])), 3)
+        row["max_abs_raw_diff"] = float((raws["x6"] - raws["bf16"]).abs().max())
+        out[str(P)] = row
+    return out
 
 
 def main():
@@ -92,9 +130,11 @@ def main():
     check["raw"] = float(raw.double().abs().sum())
     ts = timed(run)
     tf = timed(fwd)
+    fwd_ab = forward_ab(((jf, kf, 192), (jc, kc, 64)), dev)
     print(json.dumps({"lib": os.environ.get("NERF_HIP_LIB", "default"), "us_median": round(float(np.median(ts)) * 1e3, 1),
                       "us_min": round(float(np.min(ts)) * 1e3, 1), "fwd_us_median": round(float(np.median(tf)) * 1e3, 1),
-                      "fwd_us_min": round(float(np.min(tf)) * 1e3, 1), "det": det, "check": check}))
+                      "fwd_us_min": round(float(np.min(tf)) * 1e3, 1), "det": det, "check": check,
+                      "fwd_ab": fwd_ab}))
 
 if __name__ == "__main__":
     main()

@@ -30,10 +30,18 @@ DESIGN.md §16): the dense 64 + 128 frame of the unchanged path, occupancy= alon
 lattice samples per ray, each through the grid of update()'s defaults, a grid with every cell set and the scene's
 own geometry grid. Per variant: the frame time, the points the field evaluated and the PSNR.
 
+With --mlp-precision the same frame, process and method time the bf16 MLP forward instead (render(mlp_precision="bf16"),
+csrc/field_x6.hip mlp_fwd_bf16_kernel): the dense 64 + 128 frame, occupancy= alone and march= at 192
+lattice samples through the scene's own geometry grid, and march= at 192 through the grid of update()'s defaults, each
+in fp32 and in bf16. Per variant: the frame time and its ratio to the fp32 twin's, the PSNR against the target, the
+PSNR of the bf16 frame against its fp32 twin, and from one extra frame with a pair of device events around every
+launch the time of the MLP forward launches and their share of all launches' time.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
        python tools/render_time.py --march [--out profiles/march_render_time.json]
+       python tools/render_time.py --mlp-precision [--out profiles/mlp_bf16_render_time.json]
 """
 import argparse
 import json
@@ -297,6 +305,55 @@ def main_march(a):
     write(a, s, report, grid_occupied_fraction={k: g.occupied_fraction() for k, g in grids.items()})
 
 
+def launch_times(s, over):
+    """One untimed frame with a pair of device events around every launch (_lib.set_timing): {entry: ms}."""
+    from indoor_nerf_amd import _lib
+    _lib.set_timing(True)
+    try:
+        s.frame(over)
+        torch.cuda.synchronize()
+        ms = {}
+        for name, e0, e1 in _lib.timing_records():
+            ms[name] = ms.get(name, 0.0) + e0.elapsed_time(e1)
+    finally:
+        _lib.set_timing(False)
+    return ms
+
+
+def main_mlp_precision(a):
+    """The bf16 MLP forward table: see the module docstring."""
+    s = setup(a)
+    geo, default = s.new_grid("geometry"), s.new_grid("default")
+    pairs = [("dense", {}), ("geometry grid: occupancy alone", dict(occupancy=geo)),
+             ("geometry grid: march, K = 192", dict(march=geo, march_samples=192)),
+             ("default grid: march, K = 192", dict(march=default, march_samples=192))]
+    variants, twin = [], {}
+    for name, over in pairs:
+        variants += [(name, over), (name + ", bf16", dict(over, mlp_precision="bf16"))]
+        twin[name + ", bf16"] = name
+
+    report, images = {}, {}
+    for name, over in variants:         # untimed frames: PSNR, and where the launches' time goes
+        images[name] = s.frame(over)[0]
+        ms = launch_times(s, over)
+        mlp = sum(v for k, v in ms.items() if k.startswith("nerf_mlp_fwd"))
+        report[name] = dict(mlp_precision=over.get("mlp_precision", "fp32"), psnr_db=s.psnr(images[name]),
+                            mlp_fwd_launch_ms=mlp, all_launches_ms=sum(ms.values()),
+                            mlp_share_of_launch_time=mlp / max(sum(ms.values()), 1e-9),
+                            launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+        if name in twin:
+            d = (images[name] - images[twin[name]]).double()
+            report[name]["psnr_vs_fp32_twin_db"] = float(-10.0 * torch.log10((d ** 2).mean()))
+            report[name]["max_abs_rgb_diff_vs_fp32_twin"] = float(d.abs().max())
+            worst = d.abs().reshape(-1, 3).amax(-1)
+            report[name]["pixels_off_fp32_twin_by_more_than"] = {str(t): int((worst > t).sum()) for t in (1e-3, 1e-2, 1e-1)}
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_fp32_twin"] = float(np.median(times[name]) / np.median(times[base]))
+    write(a, s, report, grid_occupied_fraction={"geometry grid": geo.occupied_fraction(),
+                                                "default grid": default.occupied_fraction()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -308,8 +365,10 @@ def main():
     ap.add_argument("--early-stop", action="store_true", help="time early ray termination (DESIGN.md §14)")
     ap.add_argument("--ray-bounds", action="store_true", help="time per-ray sample bounds (DESIGN.md §15)")
     ap.add_argument("--march", action="store_true", help="time grid ray marching (DESIGN.md §16)")
+    ap.add_argument("--mlp-precision", action="store_true", help="time the bf16 MLP forward (DESIGN.md §17)")
     a = ap.parse_args()
-    mode, out = ((main_march, "profiles/march_render_time.json") if a.march else
+    mode, out = ((main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
+                 (main_march, "profiles/march_render_time.json") if a.march else
                  (main_early_stop, "profiles/early_stop_render_time.json") if a.early_stop else
                  (main_ray_bounds, "profiles/ray_bounds_render_time.json") if a.ray_bounds else
                  (main_occupancy, "bench_out/render_time.json"))
