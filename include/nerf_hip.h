@@ -79,6 +79,24 @@ int nerf_hash_encode_fwd_q(const float* d_xyz, int64_t n_points,
                            float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
                            uint8_t* d_keep, void* stream);
 
+/* Forward-only rendering with fp16 tables (additive, ABI 12). The image of n_levels tables is one
+ * device buffer of nerf_hash_half_bytes = n_levels * 2^log2_T * 4 bytes (0 for n_levels or log2_T out of range):
+ * level l at byte l * 2^log2_T * 4, entry h one 4-byte {f16 x, f16 y}.
+ * nerf_hash_tables_to_half writes it in one launch: every fp32 value rounded once to IEEE binary16, round to
+ * nearest even (subnormals kept, finite values past 65504 become +-inf, NaN stays NaN).
+ * nerf_hash_encode_fwd_half is nerf_hash_encode_fwd with the image in place of the pointer array: same checks,
+ * same grid, same voxel math, blend and keep rule, an empty batch accepts NULL per-point buffers; a gathered
+ * entry is widened to fp32 exactly. d_feat and d_keep are therefore, bit for bit, nerf_hash_encode_fwd's on
+ * tables whose values were rounded to binary16 and widened back. There is no backward for it. */
+size_t nerf_hash_half_bytes(int n_levels, int log2_T);
+int nerf_hash_tables_to_half(const float* const* d_tables, int n_levels, int log2_T, void* d_half, void* stream);
+int nerf_hash_encode_fwd_half(const float* d_xyz, int64_t n_points,
+                              const float* bbox_min3, const float* bbox_max3,
+                              const float* level_res, int n_levels, int log2_T,
+                              const void* d_half,
+                              float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                              uint8_t* d_keep, void* stream);
+
 /* d_dtables: host array of n_levels device pointers; gradients are ACCUMULATED (atomic adds). */
 int nerf_hash_encode_bwd(const float* d_xyz, int64_t n_points,
                          const float* bbox_min3, const float* bbox_max3,

@@ -136,6 +136,9 @@ SIGNATURES = {
                              c_vp, c_i64, c_i64, c_vp, c_vp],
     "nerf_hash_encode_fwd_q": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, ctypes.POINTER(c_vp), c_vp,
                                c_vp, c_i64, c_i64, c_vp, c_vp],
+    "nerf_hash_tables_to_half": [ctypes.POINTER(c_vp), c_int, c_int, c_vp, c_vp],
+    "nerf_hash_encode_fwd_half": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp,
+                                  c_vp, c_i64, c_i64, c_vp, c_vp],
     "nerf_hash_encode_bwd": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp, c_i64, c_i64,
                              ctypes.POINTER(c_vp), c_vp],
     "nerf_hash_encode_bwd_ws": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp, c_i64, c_i64,
@@ -304,6 +307,9 @@ def load():
     if hasattr(lib, "nerf_mlp_h3_bytes"):   # ABI 10 (an older A/B variant may lack it)
         lib.nerf_mlp_h3_bytes.restype = ctypes.c_size_t
         lib.nerf_mlp_h3_bytes.argtypes = [c_i64]
+    if hasattr(lib, "nerf_hash_half_bytes"):   # additive, as above
+        lib.nerf_hash_half_bytes.restype = ctypes.c_size_t
+        lib.nerf_hash_half_bytes.argtypes = [c_int, c_int]
     for name, argtypes in SIGNATURES.items():
         # a library of an older tree (an A/B variant, tools/build_variant.py --rev) may lack newer
         # entries: they stay unbound and call() raises if one is used (test_abi holds the in-tree library
@@ -325,7 +331,7 @@ def exported_symbols():
             "nerf_normal_head_bwd_workspace_bytes", "nerf_active_rows_workspace_bytes",
             "nerf_mlp_h3_bytes", "nerf_occ_compact_workspace_bytes",
             "nerf_ert_compact_workspace_bytes", "nerf_ray_span_workspace_bytes",
-            "nerf_march_workspace_bytes"] + list(SIGNATURES)
+            "nerf_march_workspace_bytes", "nerf_hash_half_bytes"] + list(SIGNATURES)
 
 
 _TIMING = None   # when a list: (name, start_event, end_event) per launch, recorded on the current stream

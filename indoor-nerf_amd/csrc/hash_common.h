@@ -264,6 +264,68 @@ __device__ __forceinline__ void fwd_finish(FwdLvl& s, int lvl, int xb, bool vali
     dst[xb] = xb ? oy_ : ox_;
 }
 
+// ---- host side of the lane-pair forward, shared by nerf_hash_encode_fwd_q (hashgrid.hip) and
+// nerf_hash_encode_fwd_half (hashgrid_half.hip): argument checks, launch parameters, grid and point ranges ----
+// Points per thread on the single-level rows (the grouped row keeps one: its levels are its
+// memory-level parallelism). Two points (p and p + 128 of the block's 256) put 8 gathers in flight
+// per thread instead of 4: per-block timelines (tools/fwd_prof.py, profiles/r05p_fwd_prof_pts*.json)
+// show each level row running as ~1.5 waves of latency-bound blocks; 92.6 -> 88.2 us per launch in
+// the bench, bit-identical (profiles/r05p_ab_fwd_row_pts2.jsonl)
+#ifndef NERF_FWD_ROW_PTS
+#define NERF_FWD_ROW_PTS 2
+#endif
+constexpr int kFwdRowPts = NERF_FWD_ROW_PTS;
+
+// The checks of a forward entry `who` before any launch (tables_given: its table argument is not null), then
+// everything of HashParams but the table pointers, and the number of grouped coarse levels. An empty batch
+// passes with NULL per-point buffers; the caller returns NERF_OK for it without a launch.
+static int fwd_host_params(const char* who, const float* d_xyz, int64_t n_points, const float* bbox_min3,
+                           const float* bbox_max3, const float* level_res, int n_levels, int log2_T,
+                           bool tables_given, const float* d_feat, HashParams& hp, int& group) {
+    NERF_REQUIRE(n_points >= 0, "%s: n_points < 0", who);
+    NERF_REQUIRE(n_levels >= 1 && n_levels <= NERF_MAX_LEVELS, "%s: n_levels %d", who, n_levels);
+    NERF_REQUIRE(log2_T >= 1 && log2_T <= 30, "%s: log2_T %d", who, log2_T);
+    NERF_REQUIRE((n_points == 0 || (d_xyz && d_feat)) && tables_given && level_res && bbox_min3 && bbox_max3,
+                 "%s: null arg", who);
+    for (int a = 0; a < 3; ++a) { hp.bmin[a] = bbox_min3[a]; hp.bmax[a] = bbox_max3[a]; }
+    hp.fastdiv = fill_cells(hp.cell, hp.rcell, bbox_min3, bbox_max3, level_res, n_levels) ? 1u : 0u;
+    hp.mask = (uint32_t)((1u << log2_T) - 1u);
+    // coarse levels grouped into one grid row: the leading levels whose (res + 1)^3 vertices fit the
+    // table (no hash collisions, a small set of hot lines)
+    group = 0;
+    while (group < (n_levels < kFwdGroupMax ? n_levels : kFwdGroupMax)) {
+        const double v = (double)level_res[group] + 1.0;
+        if (v * v * v > (double)(1u << log2_T)) break;
+        ++group;
+    }
+    if (group < 2) group = 0;
+    return NERF_OK;
+}
+
+// One-dimensional grid over every level row (blocks [0, gx0) the grouped row of 128 points each, then gx1
+// blocks of 128 row_pts points per single-level row): gridDim.x * 256 work-items must stay below 2^32, so a
+// call of more points than one launch holds runs as consecutive point ranges (rows stay level-major inside
+// each). launch(p0, n, blocks, gx0, gx1) launches points [p0, p0 + n) and returns a NERF_ code.
+template <typename Launch>
+static int fwd_for_ranges(int64_t n_points, int n_levels, int group, int row_pts, Launch&& launch) {
+    auto blocks = [&](int64_t n, unsigned& gx0, unsigned& gx1) {
+        gx0 = group > 0 ? (unsigned)blocks_for(2 * n, 256) : 0u;
+        gx1 = (unsigned)blocks_for(2 * n, 256 * row_pts);
+        return (uint64_t)gx0 + (uint64_t)gx1 * (uint64_t)(n_levels - (group > 0 ? group : 0));
+    };
+    constexpr uint64_t kMaxBlocks = 0xFFFFFFFFull / 256;
+    int64_t span = n_points;
+    unsigned gx0, gx1;
+    while (blocks(span, gx0, gx1) > kMaxBlocks) span = ((span / 2) + 255) & ~(int64_t)255;
+    for (int64_t p0 = 0; p0 < n_points; p0 += span) {
+        const int64_t n = n_points - p0 < span ? n_points - p0 : span;
+        const unsigned nb = (unsigned)blocks(n, gx0, gx1);
+        const int rc = launch(p0, n, nb, gx0, gx1);
+        if (rc != NERF_OK) return rc;
+    }
+    return NERF_OK;
+}
+
 // ---- TV loss over a hashed cuboid per level (loss.py:11-43): optim.hip (forward, atomic backward)
 // and hashgrid.hip (binned backward) -----------------------------------------------------------
 struct TVParams {

@@ -115,16 +115,7 @@ constexpr int kFwdProfBlocks = 65536;
 __device__ unsigned long long fwd_prof[kFwdProfBlocks * 3];
 #endif
 
-// Points per thread on the single-level rows (the grouped row keeps one: its levels are its
-// memory-level parallelism). Two points (p and p + 128 of the block's 256) put 8 gathers in flight
-// per thread instead of 4: per-block timelines (tools/fwd_prof.py, profiles/r05p_fwd_prof_pts*.json)
-// show each level row running as ~1.5 waves of latency-bound blocks; 92.6 -> 88.2 us per launch in
-// the bench, bit-identical (profiles/r05p_ab_fwd_row_pts2.jsonl)
-#ifndef NERF_FWD_ROW_PTS
-#define NERF_FWD_ROW_PTS 2
-#endif
-constexpr int kFwdRowPts = NERF_FWD_ROW_PTS;
-
+// Points per thread on the single-level rows: kFwdRowPts (hash_common.h).
 // Grid: one dimension, rows in order — blocks [0, gx0) the grouped row (128 points each), then gx1
 // blocks (128 kFwdRowPts points each) per single-level row (group == 0: gx1 per level from block 0).
 template <bool QUANT>
@@ -1018,44 +1009,19 @@ extern "C" int nerf_hash_encode_fwd_q(const float* d_xyz, int64_t n_points, cons
                                       const float* const* d_tables, const float* d_qrec, float* d_feat,
                                       int64_t feat_stride_point, int64_t feat_stride_level, uint8_t* d_keep,
                                       void* stream) {
-    NERF_REQUIRE(n_points >= 0, "hash_encode_fwd: n_points < 0");
-    NERF_REQUIRE(n_levels >= 1 && n_levels <= NERF_MAX_LEVELS, "hash_encode_fwd: n_levels %d", n_levels);
-    NERF_REQUIRE(log2_T >= 1 && log2_T <= 30, "hash_encode_fwd: log2_T %d", log2_T);
-    NERF_REQUIRE((n_points == 0 || (d_xyz && d_feat)) && d_tables && level_res && bbox_min3 && bbox_max3, "hash_encode_fwd: null arg");
-    if (n_points == 0) return NERF_OK;
     HashParams hp{};
+    int group = 0;
+    const int rc = fwd_host_params("hash_encode_fwd", d_xyz, n_points, bbox_min3, bbox_max3, level_res, n_levels,
+                                   log2_T, d_tables != nullptr, d_feat, hp, group);
+    if (rc != NERF_OK || n_points == 0) return rc;
     for (int l = 0; l < n_levels; ++l) {
         NERF_REQUIRE(d_tables[l], "hash_encode_fwd: table %d is null", l);
         hp.tables[l] = d_tables[l];
     }
-    for (int a = 0; a < 3; ++a) { hp.bmin[a] = bbox_min3[a]; hp.bmax[a] = bbox_max3[a]; }
-    hp.fastdiv = fill_cells(hp.cell, hp.rcell, bbox_min3, bbox_max3, level_res, n_levels) ? 1u : 0u;
-    hp.mask = (uint32_t)((1u << log2_T) - 1u);
     const QuantRec* q = reinterpret_cast<const QuantRec*>(d_qrec);
-    // coarse levels grouped into one grid row: the leading levels whose (res + 1)^3 vertices fit the
-    // table (no hash collisions, a small set of hot lines)
-    int group = 0;
-    while (group < std::min(n_levels, kFwdGroupMax)) {
-        const double v = (double)level_res[group] + 1.0;
-        if (v * v * v > (double)(1u << log2_T)) break;
-        ++group;
-    }
-    if (group < 2) group = 0;
-    // one-dimensional grid over every level row: gridDim.x * 256 work-items must stay below 2^32, so a
-    // call of more points than one launch holds runs as consecutive point ranges (rows stay
-    // level-major inside each)
-    auto blocks = [&](int64_t n, unsigned& gx0, unsigned& gx1) {
-        gx0 = group > 0 ? (unsigned)blocks_for(2 * n, 256) : 0u;
-        gx1 = (unsigned)blocks_for(2 * n, 256 * kFwdRowPts);
-        return (uint64_t)gx0 + (uint64_t)gx1 * (uint64_t)(n_levels - (group > 0 ? group : 0));
-    };
-    constexpr uint64_t kMaxBlocks = 0xFFFFFFFFull / 256;
-    int64_t span = n_points;
-    unsigned gx0, gx1;
-    while (blocks(span, gx0, gx1) > kMaxBlocks) span = ((span / 2) + 255) & ~(int64_t)255;
-    for (int64_t p0 = 0; p0 < n_points; p0 += span) {
-        const int64_t n = std::min(span, n_points - p0);
-        const dim3 grid((unsigned)blocks(n, gx0, gx1));
+    return fwd_for_ranges(n_points, n_levels, group, kFwdRowPts,
+                          [&](int64_t p0, int64_t n, unsigned nb, unsigned gx0, unsigned gx1) -> int {
+        const dim3 grid(nb);
         uint8_t* kp = d_keep ? d_keep + p0 : nullptr;
         float* fp = d_feat + p0 * feat_stride_point;
         if (q)
@@ -1065,8 +1031,8 @@ extern "C" int nerf_hash_encode_fwd_q(const float* d_xyz, int64_t n_points, cons
             hipLaunchKernelGGL(hash_encode_fwd_pair_kernel<false>, grid, dim3(256), 0, as_stream(stream), d_xyz + 3 * p0,
                                n, hp, group, gx0, gx1, fp, feat_stride_point, feat_stride_level, kp, q);
         NERF_CHECK_LAUNCH("hash_encode_fwd");
-    }
-    return NERF_OK;
+        return NERF_OK;
+    });
 }
 
 extern "C" int nerf_hash_encode_fwd(const float* d_xyz, int64_t n_points, const float* bbox_min3,

@@ -191,6 +191,7 @@ class FieldFn(torch.autograd.Function):
         n_tab = embedder.n_levels
         tables, weights, head = params[:n_tab], params[n_tab:n_tab + 5], params[n_tab + 5:]
         bf16 = getattr(pts, "_nerf_mlp", None) is not None   # run_network's checked MlpRequest
+        half = getattr(pts, "_nerf_tab", None) is not None   # and its checked TableRequest
         pts = pts.contiguous()
         sh_rays = getattr(viewdirs, "_nerf_sh", None)   # render_rays' per-ray SH4 rows (sh_stride 0)
         viewdirs = viewdirs.contiguous()
@@ -207,20 +208,20 @@ class FieldFn(torch.autograd.Function):
             # fine pass: the importance samples are gathered into the head rows of the reuse buffer, whose
             # tail holds the coarse pass's features; the MLP walks that importance-first order
             feat, keep, row0 = reuse.feat, reuse.keep, 0
-            embedder.encode_into(reuse.imp_pts.view(-1, 3), feat, 2, 2 * P, keep)
+            embedder.encode_into(reuse.imp_pts.view(-1, 3), feat, 2, 2 * P, keep, half=half)
             order = (reuse.inv, reuse.R * reuse.N, reuse.S)
             spr = reuse.N
             reuse.state = "used"
             ctx.reuse = ("fine", reuse)
         elif reuse is not None and plain and reuse.state == "armed" and P == reuse.R * reuse.S:
             feat, keep, row0 = reuse.alloc(n_tab, dev)      # coarse pass: the tail rows of the reuse buffer
-            embedder.encode_into(pts, feat, 2, 2 * feat.shape[1], keep, row0=row0)
+            embedder.encode_into(pts, feat, 2, 2 * feat.shape[1], keep, row0=row0, half=half)
             reuse.record(pts, embedder, tables)
             ctx.reuse = ("coarse", reuse)
         else:
             feat = torch.empty(n_tab, P, 2, device=dev, dtype=torch.float32)
             keep, row0 = torch.empty(P, device=dev, dtype=torch.bool), 0
-            embedder.encode_into(pts, feat, 2, 2 * P, keep)
+            embedder.encode_into(pts, feat, 2, 2 * P, keep, half=half)
         sl = 2 * feat.shape[1]
         keep = keep[row0:row0 + P]                   # the MLP's keep flags, in its point order
         raw = torch.empty(P, 4, device=dev, dtype=torch.float32)
@@ -654,16 +655,22 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
     netchunk is then only a memory knob the fused kernels do not need."""
     sparse = getattr(inputs, "_nerf_sparse", None)   # sparse_field.SparseRequest of this render_rays call
     mlp = getattr(inputs, "_nerf_mlp", None)         # sparse_field.MlpRequest of it (mlp_precision="bf16")
+    tab = getattr(inputs, "_nerf_tab", None)         # sparse_field.TableRequest of it (table_precision="fp16")
     if mlp is not None:
         mlp.used = True
+    if tab is not None:
+        tab.used = True
     if sparse is not None:
         from .sparse_field import run_network_sparse
         sparse.used = True
-        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse, mlp)
+        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse, mlp, tab)
     call_ok = isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3
     if mlp is not None:   # never the eager path below, and never fp32 silently
         from .sparse_field import check_mlp_field
         check_mlp_field(call_ok, "inputs [R, S, 3]", fn, embed_fn)
+    if tab is not None:   # likewise: never the eager path, never the fp32 tables silently
+        from .sparse_field import check_table_field
+        check_table_field(call_ok, "inputs [R, S, 3]", fn, embed_fn)
     fused = isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall) and call_ok
     if fused:
         if embed_fn.training:
@@ -673,9 +680,13 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
         flat = inputs.reshape(-1, 3)
         if mlp is not None:
             flat._nerf_mlp = mlp
+        if tab is not None:
+            flat._nerf_tab = tab
         raw = FieldFn.apply(flat, viewdirs, S, embed_fn, fn, netchunk, reuse, *embed_fn.tables(), *fn.field_params())
         if mlp is not None:
             del flat._nerf_mlp
+        if tab is not None:
+            del flat._nerf_tab
         out = raw.reshape(R, S, fn.raw_channels)
         # without a normals head FieldFn's backward only queues its job: raw2outputs may then defer the
         # compositing backward too (render.CompositeJob)

@@ -539,6 +539,9 @@ def hash_encode_bwd(xyz, meta, dfeat, sp, sl, grad_tables, defer=None, queue=Tru
               _lib.ptr(ws, "workspace", dtype=torch.uint8, allow_none=True), nbytes, _lib.stream())
 
 
+HALF_ACAQ = "encode_into: half tables are not available with A-CAQ quantizers (they have their own packed tables)"
+
+
 class HashEmbedder(nn.Module):
     """hash_encoding.py:11-107 on MI355X. forward(x [P,3]) -> (feat [P, L*F], keep [P] bool)."""
 
@@ -558,6 +561,7 @@ class HashEmbedder(nn.Module):
         self.out_dim = n_levels * n_features_per_level
         self.use_quantization = use_quantization
         self._packed = None
+        self._half = None
         self.warmup_steps = 500
         self.current_step = 0
         res, self.b = level_resolutions(self.base_resolution, self.finest_resolution, n_levels)
@@ -638,16 +642,44 @@ class HashEmbedder(nn.Module):
         st["key"] = key
         return st["buf"], rec
 
-    def encode_into(self, xyz, feat, sp, sl, keep, row0=0):
+    def half_tables(self):
+        """The fp16 image of the tables for forward-only rendering (table_precision="fp16", DESIGN.md §18;
+        csrc/hashgrid_half.hip): one uint8 buffer per device, level l at byte l * T * 4, each value rounded once to
+        binary16. No host sync: it is rebuilt (nerf_hash_tables_to_half, one launch) only when a table changed
+        (packed_tables' key: data pointers and torch version counters, which the HIP kernels that write tables in
+        place bump, see optim.RAdam). Neither a parameter nor a buffer: state_dict() does not hold it."""
+        tabs = self.tables()
+        key = tuple((t.data_ptr(), t._version) for t in tabs)
+        dev = tabs[0].device
+        join_tables(dev)
+        st = self._half
+        if st is None or st["buf"].device != dev:
+            nbytes = int(_lib.load().nerf_hash_half_bytes(self.n_levels, self.log2_hashmap_size))
+            st = self._half = dict(buf=torch.empty(nbytes, dtype=torch.uint8, device=dev), key=None)
+        if st["key"] != key:
+            _lib.call("nerf_hash_tables_to_half", _lib.ptr_array(tabs), self.n_levels, self.log2_hashmap_size,
+                      _lib.ptr(st["buf"], "half_tables", dtype=torch.uint8), _lib.stream())
+            st["key"] = key
+        return st["buf"]
+
+    def encode_into(self, xyz, feat, sp, sl, keep, row0=0, half=False):
         """Forward gather into caller-allocated feat/keep on the path this forward needs: plain,
         fake-quantized (training / STE) or int-packed (eval-mode quantizers). row0: the points land in
-        rows row0 .. row0 + n of feat (level-major, point stride sp, level stride sl) and keep."""
+        rows row0 .. row0 + n of feat (level-major, point stride sp, level stride sl) and keep.
+        half (forward-only rendering): gather from half_tables() instead of the fp32 tables."""
+        if half and self.quantization_active():
+            raise ValueError(HALF_ACAQ)
         meta = self._meta
         P = xyz.shape[0]
         if P > 0 and ((row0 + P - 1) * sp + (self.n_levels - 1) * sl + 2 > feat.numel() or row0 + P > keep.numel()):
             raise ValueError("encode_into: rows out of the feature / keep buffers")
         fp = _lib.ptr_at(feat, sp * row0, "feat")
         kp = _lib.ptr_at(keep, row0, "keep", dtype=torch.bool)
+        if half:
+            _lib.call("nerf_hash_encode_fwd_half", _lib.ptr(xyz, "xyz"), P, meta["bmin"], meta["bmax"], meta["res"],
+                      self.n_levels, meta["log2_T"], _lib.ptr(self.half_tables(), "half_tables", dtype=torch.uint8),
+                      fp, sp, sl, kp, _lib.stream())
+            return
         key, L = str(xyz.device), self.n_levels
         plain = not self.quantization_active()
         gates = _GATES.pop(key, []) if plain else []

@@ -374,27 +374,45 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return out
 
 
-def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16):
-    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16")."""
-    if not bf16:
+def _query_tab(network_query_fn, pts, viewdirs, fn, half):
+    """network_query_fn(pts, viewdirs, fn); half: with a TableRequest on the points (table_precision="fp16")."""
+    if not half:
         return network_query_fn(pts, viewdirs, fn)
+    from .sparse_field import TableRequest
+    req = pts._nerf_tab = TableRequest()
+    try:
+        raw = network_query_fn(pts, viewdirs, fn)
+    finally:
+        del pts._nerf_tab
+    if not req.used:   # a foreign query function ignores the attribute: never read the fp32 tables silently
+        raise ValueError("render_rays: table_precision needs a network_query_fn that calls this package's run_network")
+    return raw
+
+
+def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half=False):
+    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16"); half:
+    with a TableRequest beside it (_query_tab)."""
+    if not bf16:
+        return _query_tab(network_query_fn, pts, viewdirs, fn, half)
     from .sparse_field import MlpRequest
     req = pts._nerf_mlp = MlpRequest()
-    raw = network_query_fn(pts, viewdirs, fn)
-    del pts._nerf_mlp
+    try:
+        raw = _query_tab(network_query_fn, pts, viewdirs, fn, half)
+    finally:
+        del pts._nerf_mlp
     if not req.used:   # a foreign query function ignores the attribute: never render in fp32 silently
         raise ValueError("render_rays: mlp_precision needs a network_query_fn that calls this package's run_network")
     return raw
 
 
-def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False):
+def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False, half=False):
     """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
     (stops int32 [R], early_stop.py), None otherwise (stops None)."""
     if occupancy is None and early is None:
-        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16), None
+        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half), None
     from .sparse_field import SparseRequest
     req = pts._nerf_sparse = SparseRequest(occupancy, early)
-    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16)
+    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half)
     del pts._nerf_sparse
     if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
         raise ValueError(f"render_rays: {req.what} needs a network_query_fn that calls this package's run_network")
@@ -411,7 +429,8 @@ def last_early_stop_counts():
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False, lindisp=False,
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
-                march=None, march_samples=512, march_points=1 << 21, mlp_precision=None):
+                march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
+                table_precision=None):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -432,7 +451,18 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     mlp_precision (None, "fp32" or "bf16"; forward-only rendering): "bf16" runs every MLP forward
     of the call with one bf16 piece per operand and fp32 sums (nerf_mlp_fwd_bf16) instead of the fp32-accurate
     kernel: weights, hash features, SH and hidden activations are rounded to bf16, sigma and the colour layer's
-    sums stay fp32. Composes with occupancy=, early_stop= and march=. None and "fp32" are the call without it."""
+    sums stay fp32. Composes with occupancy=, early_stop= and march=. None and "fp32" are the call without it.
+    table_precision (None, "fp32" or "fp16"; forward-only rendering): "fp16" makes every hash-encoding
+    launch of the call gather from an fp16 image of the tables (HashEmbedder.half_tables, nerf_hash_encode_fwd_half):
+    each table value rounded once to binary16, everything else unchanged, so the result is bit for bit the default
+    render of a model whose tables are t.half().float(). Composes with occupancy=, early_stop=, march= and
+    mlp_precision=. None and "fp32" are the call without it."""
+    half = False
+    if table_precision is not None:
+        from .sparse_field import check_table_nets, check_table_precision
+        half = check_table_precision(table_precision, "render_rays")
+    if half:
+        check_table_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn)
     bf16 = False
     if mlp_precision is not None:
         from .sparse_field import check_mlp_nets, check_mlp_precision
@@ -444,7 +474,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  bf16=bf16)
+                                  bf16=bf16, half=half)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -483,7 +513,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
     raw, stops = _query(network_query_fn, pts, viewdirs, network_fn, occupancy,
-                        None if early is None else (z, rays_d) + early, bf16)
+                        None if early is None else (z, rays_d) + early, bf16, half)
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -525,7 +555,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
             pts._nerf_reuse = reuse
         stops0 = stops
         raw, stops = _query(network_query_fn, pts, viewdirs, run_fn, occupancy,
-                            None if early is None else (z, rays_d) + early, bf16)
+                            None if early is None else (z, rays_d) + early, bf16, half)
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()
@@ -586,7 +616,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None, bf16=False):
+                       predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing."""
     run_fn = network_fn if network_fine is None else network_fine
@@ -602,7 +632,7 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     f = dict(device=dev, dtype=torch.float32)
     if n > 0:
         req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
-        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16)
+        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half)
         del pts_c._nerf_sparse
         if not req.used:   # a foreign query function ignores the attribute: never fall back silently
             raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
@@ -779,8 +809,8 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     ray_hit (bool) and ray_span ([near', far'] per ray). Composes with occupancy= and early_stop=. None (the
     default) leaves the call as it is without it.
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
-    spans its own [near', far']. mlp_precision goes to render_rays as well. retraw is refused with
-    march: the packed entries of several chunks do not concatenate."""
+    spans its own [near', far']. mlp_precision and table_precision go to
+    render_rays as well. retraw is refused with march: the packed entries of several chunks do not concatenate."""
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")
@@ -789,6 +819,11 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     if kwargs.get("mlp_precision") is not None:   # also when no chunk reaches render_rays (ray_bounds with every ray missed)
         from .sparse_field import check_mlp_precision
         check_mlp_precision(kwargs["mlp_precision"], "render")
+    if kwargs.get("table_precision") is not None:   # likewise
+        from .sparse_field import check_table_nets, check_table_precision
+        if check_table_precision(kwargs["table_precision"], "render"):
+            nets = [kwargs[k] for k in ("network_fn", "network_fine") if kwargs.get(k) is not None]
+            check_table_nets(nets, kwargs.get("embed_fn"), "render")
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, K, c2w)
     else:

@@ -17,7 +17,8 @@ from .occupancy import _check_modules
 # why each keyword is forward-only (check_forward_only's and _begin_field_call's refusals)
 NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training",
                    "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training",
-                   "mlp_precision": "the backward recomputes the forward in fp32"}
+                   "mlp_precision": "the backward recomputes the forward in fp32",
+                   "table_precision": "the backward scatters into the fp32 tables"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -103,6 +104,59 @@ def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order):
         _lib.call("nerf_mlp_fwd_ord", *front, None, None, None, 0, order, _lib.stream())
 
 
+class TableRequest:
+    """render_rays' request of the fp16 hash tables (table_precision="fp16"), attached to the point
+    tensor of every pass as `pts._nerf_tab`, beside an MlpRequest and a SparseRequest / MarchRequest when there are
+    any. run_network sets `used` (a foreign query function leaves it False and render_rays raises) and routes every
+    hash-encoding launch of the call to nerf_hash_encode_fwd_half (HashEmbedder.encode_into(half=True))."""
+    what = "table_precision"
+
+    def __init__(self):
+        self.used = False
+
+
+def check_table_precision(value, prefix):
+    """table_precision of `prefix` (render_rays, render) -> whether it asks for the fp16 tables; its refusals: an
+    unknown value, gradients enabled. Raw noise is fine: the encoding does not care."""
+    if value is None or (isinstance(value, str) and value == "fp32"):
+        return False
+    if not (isinstance(value, str) and value == "fp16"):
+        raise ValueError(f"{prefix}: table_precision must be None, 'fp32' or 'fp16', got {value!r}")
+    check_forward_only("table_precision", prefix)
+    return True
+
+
+def _check_table_modules(embed_fn, fn, what):
+    """The modules the fp16 gather can serve: the fused field's, with plain fp32 tables. A normals head and a
+    quantized MLP are fine: the encoding does not care."""
+    from .field import NeRFSmall
+    from .hashgrid import HashEmbedder
+    if not isinstance(embed_fn, HashEmbedder) or not isinstance(fn, NeRFSmall):
+        raise ValueError(f"{what}: needs the fused field modules (HashEmbedder + NeRFSmall), got "
+                         f"{type(embed_fn).__name__} + {type(fn).__name__}")
+    if embed_fn.use_quantization:
+        raise ValueError(f"{what}: A-CAQ quantizers are not supported (they have their own packed tables)")
+
+
+def check_table_nets(nets, embed_fn, prefix="render_rays"):
+    """render_rays' refusals with table_precision="fp16" that need its modules: before any launch, for the
+    networks of every pass."""
+    if embed_fn is not None:
+        for fn in nets:
+            _check_table_modules(embed_fn, fn, f"{prefix}: table_precision")
+
+
+def check_table_field(call_ok, shape_words, fn, embed_fn):
+    """The dense run_network's refusals for a TableRequest, all before any launch (call_ok: SHEncoder view
+    encoding, viewdirs and the inputs that shape_words describes)."""
+    what = TableRequest.what
+    if not call_ok:
+        raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
+    _check_table_modules(embed_fn, fn, what)
+    if torch.is_grad_enabled():
+        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+
+
 def check_march_points(m):
     if isinstance(m, bool) or not isinstance(m, int) or m < 1:
         raise ValueError(f"march: march_points must be a positive integer, got {m!r}")
@@ -136,10 +190,11 @@ def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embe
         embed_fn.current_step += 1
 
 
-def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None):
+def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None, tab=None):
     """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
     raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16) run over the list in
-    slices of at most req.max_points points; a point's result does not depend on its slice."""
+    slices of at most req.max_points points; a point's result does not depend on its slice. mlp, tab: the call's
+    MlpRequest and TableRequest, or None."""
     from .field import _weights_struct
     _begin_field_call("march", inputs.dim() == 2 and req.sh_c is not None, "packed inputs [n, 3]", viewdirs, fn,
                       embed_fn, embeddirs_fn)
@@ -156,19 +211,19 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     feat, keep = torch.empty(L * m * 2, **f), torch.empty(m, device=dev, dtype=torch.bool)
     for s0 in range(0, n, m):
         k = min(m, n - s0)
-        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * 2], 2, 2 * k, keep[:k])
+        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * 2], 2, 2 * k, keep[:k], half=tab is not None)
         mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
                     _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None)
     return raw
 
 
-def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None):
+def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None, tab=None):
     """run_network (field.py) for a SparseRequest: inputs [R, S, 3], viewdirs [R, 3] -> raw [R, S, 4] with
     the field evaluated at the kept samples only and zero rows elsewhere. Without early termination the call
     is one slab through req.grid.compact; with it, slabs of req.early's size front to back, nerf_ert_advance
     between them, and req.stop receives the stops."""
     if isinstance(req, MarchRequest):
-        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp)
+        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp, tab)
     from .field import _point_order, _weights_struct
     what = req.what
     _begin_field_call(what, inputs.dim() == 3, "inputs [R, S, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
@@ -191,7 +246,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
 
     def field(n, rows, pts_c, sh_c, feat, keep):
         """The field at the n compacted points; rows of raw `rows` receive the results."""
-        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep)
+        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep, half=tab is not None)
         mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * n, _lib.ptr(sh_c, "sh_c"), _lib.ptr(keep, "keep", torch.bool), n,
                     weights, _lib.ptr(raw, "raw"), _point_order((rows, 0, 0)))
 

@@ -37,11 +37,18 @@ in fp32 and in bf16. Per variant: the frame time and its ratio to the fp32 twin'
 PSNR of the bf16 frame against its fp32 twin, and from one extra frame with a pair of device events around every
 launch the time of the MLP forward launches and their share of all launches' time.
 
+With --table-precision the same frame, process and method time the fp16 hash tables instead (render(table_precision=
+"fp16"), csrc/hashgrid_half.hip): the four rows of --mlp-precision, each with fp32 and fp16 tables under
+both mlp_precision settings. Per variant: the frame time and its ratio to the fp32-table twin's, the PSNR against the
+target, the PSNR of the fp16-table frame against its fp32-table twin, and from one extra frame with a pair of device
+events around every launch the time of the hash-encoding launches and their share of all launches' time.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
        python tools/render_time.py --march [--out profiles/march_render_time.json]
        python tools/render_time.py --mlp-precision [--out profiles/mlp_bf16_render_time.json]
+       python tools/render_time.py --table-precision [--out profiles/table_fp16_render_time.json]
 """
 import argparse
 import json
@@ -354,6 +361,45 @@ def main_mlp_precision(a):
                                                 "default grid": default.occupied_fraction()})
 
 
+def main_table_precision(a):
+    """The fp16 hash-table table: see the module docstring."""
+    s = setup(a)
+    geo, default = s.new_grid("geometry"), s.new_grid("default")
+    rows = [("dense", {}), ("geometry grid: occupancy alone", dict(occupancy=geo)),
+            ("geometry grid: march, K = 192", dict(march=geo, march_samples=192)),
+            ("default grid: march, K = 192", dict(march=default, march_samples=192))]
+    variants, twin = [], {}
+    for mlp in ("fp32", "bf16"):
+        for name, over in rows:
+            base = name if mlp == "fp32" else name + ", bf16 MLP"
+            over = dict(over) if mlp == "fp32" else dict(over, mlp_precision="bf16")
+            variants += [(base, over), (base + ", fp16 tables", dict(over, table_precision="fp16"))]
+            twin[base + ", fp16 tables"] = base
+
+    report, images = {}, {}
+    for name, over in variants:         # untimed frames: PSNR, and where the launches' time goes
+        images[name] = s.frame(over)[0]
+        ms = launch_times(s, over)
+        enc = sum(v for k, v in ms.items() if k.startswith("nerf_hash_encode_fwd"))
+        report[name] = dict(mlp_precision=over.get("mlp_precision", "fp32"),
+                            table_precision=over.get("table_precision", "fp32"), psnr_db=s.psnr(images[name]),
+                            hash_fwd_launch_ms=enc, all_launches_ms=sum(ms.values()),
+                            hash_share_of_launch_time=enc / max(sum(ms.values()), 1e-9),
+                            launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+        if name in twin:
+            d = (images[name] - images[twin[name]]).double()
+            report[name]["psnr_vs_fp32_table_twin_db"] = float(-10.0 * torch.log10((d ** 2).mean()))
+            report[name]["max_abs_rgb_diff_vs_fp32_table_twin"] = float(d.abs().max())
+            worst = d.abs().reshape(-1, 3).amax(-1)
+            report[name]["pixels_off_fp32_table_twin_by_more_than"] = {str(t): int((worst > t).sum())
+                                                                       for t in (1e-3, 1e-2, 1e-1)}
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_fp32_table_twin"] = float(np.median(times[name]) / np.median(times[base]))
+    write(a, s, report, grid_occupied_fraction={"geometry grid": geo.occupied_fraction(),
+                                                "default grid": default.occupied_fraction()})
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -366,8 +412,10 @@ def main():
     ap.add_argument("--ray-bounds", action="store_true", help="time per-ray sample bounds (DESIGN.md §15)")
     ap.add_argument("--march", action="store_true", help="time grid ray marching (DESIGN.md §16)")
     ap.add_argument("--mlp-precision", action="store_true", help="time the bf16 MLP forward (DESIGN.md §17)")
+    ap.add_argument("--table-precision", action="store_true", help="time the fp16 hash tables (DESIGN.md §18)")
     a = ap.parse_args()
-    mode, out = ((main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
+    mode, out = ((main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
+                 (main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
                  (main_march, "profiles/march_render_time.json") if a.march else
                  (main_early_stop, "profiles/early_stop_render_time.json") if a.early_stop else
                  (main_ray_bounds, "profiles/ray_bounds_render_time.json") if a.ray_bounds else
