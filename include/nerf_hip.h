@@ -935,6 +935,43 @@ int nerf_march_composite(const float* d_raw, const float* d_z, const float* d_di
                          const float* d_rays_d, int64_t n_rays, int64_t n_points, int white_bkgd, float* d_rgb,
                          float* d_disp, float* d_acc, float* d_depth, float* d_weights, void* stream);
 
+/* ---- stopping opaque rays inside the grid march (csrc/march.hip) ---------------
+ * Additive entries (the ABI version stays 12). The n_samples lattice indices of a march run front to back in
+ * slabs [k0, k1), 0 <= k0 <= k1 <= n_samples; d_alive [n_rays] (uint8) holds which rays are still walked.
+ *
+ * nerf_slab_march_count, nerf_slab_march_write: nerf_march_count and nerf_march_write over the lattice indices
+ *   k0 <= k < k1 of the rays with d_alive[r] != 0 (d_alive NULL: every ray); a ray with d_alive[r] == 0 counts
+ *   0. dist_k is still the distance to the next sample of the whole lattice (1e10 for k = n_samples - 1 only).
+ *   With 0, n_samples, NULL they are nerf_march_count and nerf_march_write bit for bit. The write takes the
+ *   counts and offsets the count left and needs no flags; n_points <= n_rays * (k1 - k0).
+ * nerf_slab_march_composite: nerf_march_composite of one slab's list with the per-ray state d_state
+ *   [n_rays, 6] (double: the transmittance carried, the sums of w c (3), of w and of w z), which is read unless
+ *   `first` and written unless `last`; d_rgb, d_disp, d_acc and d_depth are written on `last` only (d_weights,
+ *   optional, for every slab's own list). first = last = 1 is nerf_march_composite bit for bit.
+ * nerf_slab_march_advance: the stopping rule after a slab that is not the last. For every ray with
+ *   d_alive[r] != 0, in fp32 and in entry order (no fused multiply-add): norm = sqrtf(dx*dx + dy*dy + dz*dz)
+ *   of d_rays_d; for each entry e of [d_offsets[r], d_offsets[r + 1]): d_tau[r] += max(sigma_e, 0) *
+ *   (d_dist[e] * norm) with sigma_e = d_raw[e, 3] (NaN counts as 0); then, if d_tau[r] > tau_max (> 0):
+ *   d_alive[r] = 0 and d_stop[r] = s1 (int32; 0 <= s1 <= 4096, the slab's end).
+ * n_rays = 0 (and, for the write, n_points = 0) launches nothing and accepts NULL buffers. */
+int nerf_slab_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                          int64_t k0, int64_t k1, const uint8_t* d_alive, const float* bbox_min,
+                          const float* bbox_max, int res, const uint32_t* d_bits, int32_t* d_counts,
+                          int32_t* d_offsets, float* d_rays_d, void* d_workspace, size_t workspace_bytes,
+                          void* stream);
+int nerf_slab_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                          int64_t k0, int64_t k1, const float* bbox_min, const float* bbox_max, int res,
+                          const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets,
+                          int64_t n_points, int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c,
+                          float* d_sh_c, void* stream);
+int nerf_slab_march_composite(const float* d_raw, const float* d_z, const float* d_dist, const int32_t* d_offsets,
+                              const float* d_rays_d, int64_t n_rays, int64_t n_points, int white_bkgd,
+                              double* d_state, int first, int last, float* d_rgb, float* d_disp, float* d_acc,
+                              float* d_depth, float* d_weights, void* stream);
+int nerf_slab_march_advance(const float* d_raw, const float* d_dist, const int32_t* d_offsets,
+                            const float* d_rays_d, int64_t n_rays, int64_t n_points, int64_t s1, float tau_max,
+                            float* d_tau, uint8_t* d_alive, int32_t* d_stop, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

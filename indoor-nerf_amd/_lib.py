@@ -258,6 +258,13 @@ SIGNATURES = {
     "nerf_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_i64, c_i64,
                          c_vp, c_vp, c_vp, c_vp, c_vp],
     "nerf_march_composite": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nerf_slab_march_count": [c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64, c_vp, c_f32p, c_f32p, c_int, c_vp, c_vp,
+                              c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp],
+    "nerf_slab_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp,
+                              c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nerf_slab_march_composite": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_int, c_int, c_vp, c_vp,
+                                  c_vp, c_vp, c_vp, c_vp],
+    "nerf_slab_march_advance": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
 }
 
 _lib = None

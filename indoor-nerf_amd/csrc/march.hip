@@ -12,9 +12,10 @@
 // the list, rays ascending: the list is the dense array's kept entries in row-major order.
 //
 // One wave per ray, lane l of iteration i tests lattice index 64 i + l; a ballot counts the kept lanes.
-//   nerf_march_count: counts [R] (one store per ray) and, per block of kCompactBlock rays, the sum of its counts
-//     (integer atomic adds: the sums do not depend on the order the waves run in); then off [R + 1], the
-//     exclusive scan of counts, by compact_common.h's block offsets and a scan inside each block.
+//   nerf_march_count: counts [R] (one store per ray); then, per block of kCompactBlock rays, the sum of its counts
+//     (a reduction of its own: one atomic add per ray into the few counters of a chunk, all in one cache line,
+//     took longer than the walk itself); then off [R + 1], the exclusive scan of counts, by
+//     compact_common.h's block offsets and a scan inside each block.
 //   nerf_march_write: the same walk; a kept sample's rank is off[r] + the kept samples of the ray's earlier
 //     iterations + the kept lanes below its own. Writes pts_c, z_c, dist_c and the ray's SH4 row per point.
 //   nerf_march_composite: packed forward compositing, one wave per ray, 64 entries per iteration. The
@@ -24,6 +25,21 @@
 //     earlier entries (a wave scan times a running carry); the ray sums are per-lane fp64 accumulators,
 //     reduced once. A skipped sample has alpha = 0 and t = 1.0f exactly, so leaving it out changes no
 //     product and no sum as a real number; only the fp64 association differs from the dense kernel.
+//
+// Stopping opaque rays inside the march: the K lattice indices run front to back in slabs
+// [k0, k1); a ray is walked only while its flag alive[r] is set.
+//   nerf_slab_march_count / nerf_slab_march_write: the two walks above over the lattice range [k0, k1) of the rays
+//     with alive[r] != 0 (NULL: every ray); a dead ray counts 0. dist_k still comes from the full lattice (1e10f
+//     for k = K - 1 only). nerf_march_count / nerf_march_write are these with 0, K, NULL.
+//   nerf_slab_march_composite: march_composite_kernel with a per-ray fp64 state [R, 6] (the carry, the three sums
+//     of w c, of w and of w z) read at entry unless `first` and written at exit unless `last`; the maps are
+//     written on `last`. first = last = 1 is nerf_march_composite bit for bit; over several slabs only the fp64
+//     association differs (each slab's lane sums are reduced before the next slab adds to them).
+//   nerf_slab_march_advance: the stopping rule, one thread per ray, fp32, strictly in entry order (the file is
+//     built with -ffp-contract=off): norm_d = sqrtf(dx*dx + dy*dy + dz*dz); for each entry e of the ray's segment:
+//     d = dist[e] * norm_d, s = sigma_e > 0 ? sigma_e : 0 (NaN gives 0), tau = tau + s * d; the ray dies
+//     (alive = 0, stop = s1) when tau > tau_max. early_stop.hip's rule with the packed dist in place of
+//     z[i + 1] - z[i]; a skipped lattice sample adds nothing, as a masked sigma does there.
 #include "compact_common.h"
 #include "occ_common.h"
 
@@ -39,6 +55,8 @@ struct MarchArgs {
     const float* rays;       // [R, C]
     int64_t R;
     int C, K;
+    int k0, k1;              // the lattice range walked, 0 <= k0 <= k1 <= K
+    const uint8_t* alive;    // optional [R]: a ray with alive[r] == 0 keeps nothing
     const float* t;          // [K]
     int32_t* counts;         // [R]
     int32_t* off;            // [R + 1]
@@ -81,11 +99,12 @@ __global__ void __launch_bounds__(kMarchThreads) march_count_kernel(MarchArgs a)
     const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
     if (r >= a.R) return;   // wave-uniform
     const MarchRay m = march_ray(a, r);
+    const int k1 = (a.alive && !a.alive[r]) ? a.k0 : a.k1;   // wave-uniform: a dead ray walks nothing
     int n = 0;
-    for (int k0 = 0; k0 < a.K; k0 += 64) {
-        const int k = k0 + lane;
+    for (int kb = a.k0; kb < k1; kb += 64) {
+        const int k = kb + lane;
         bool on = false;
-        if (k < a.K) {
+        if (k < k1) {
             float z, p[3];
             on = march_sample(a, m, k, z, p);
         }
@@ -93,10 +112,29 @@ __global__ void __launch_bounds__(kMarchThreads) march_count_kernel(MarchArgs a)
     }
     if (lane == 0) {
         a.counts[r] = n;
-        if (n) atomicAdd(a.block_counts + r / kCompactBlock, n);
         if (a.rays_d) {
             a.rays_d[3 * r] = m.d[0]; a.rays_d[3 * r + 1] = m.d[1]; a.rays_d[3 * r + 2] = m.d[2];
         }
+    }
+}
+
+// block_counts[b] = the counts of rays [b * kCompactBlock, (b + 1) * kCompactBlock): item = ray, every entry of the
+// workspace is written
+__global__ void __launch_bounds__(kCompactThreads) march_block_counts_kernel(MarchArgs a) {
+    int n = 0;
+    for (int k = 0; k < kCompactPer; ++k) {
+        const int64_t r = compact_item(k);
+        if (r < a.R) n += a.counts[r];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o, 64);
+    __shared__ int s[kCompactWaves];
+    if ((threadIdx.x & 63) == 0) s[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        int t = 0;
+        for (int i = 0; i < kCompactWaves; ++i) t += s[i];
+        a.block_counts[blockIdx.x] = t;
     }
 }
 
@@ -141,11 +179,11 @@ __global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a)
     }
     const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     int64_t base = a.off[r];
-    for (int k0 = 0; k0 < a.K; k0 += 64) {
-        const int k = k0 + lane;
+    for (int kb = a.k0; kb < a.k1; kb += 64) {   // a dead ray has counts[r] == 0 and never gets here
+        const int k = kb + lane;
         bool on = false;
         float z = 0.f, p[3] = {0.f, 0.f, 0.f};
-        if (k < a.K) on = march_sample(a, m, k, z, p);
+        if (k < a.k1) on = march_sample(a, m, k, z, p);
         const uint64_t mask = __ballot(on);
         const int64_t idx = base + __popcll(mask & below);
         if (on && idx >= 0 && idx < a.capacity) {
@@ -173,11 +211,15 @@ struct MarchCompositeArgs {
     int white;
     float* rgb; float* disp; float* acc; float* depth;   // [R, 3], [R], [R], [R]
     float* weights;          // optional [n]
+    double* state;           // slabs only: [R, 6] = carry, sum w c (3), sum w, sum w z
+    int first, last;         // slabs only: state is not read on first, the maps are written on last
 };
 
 // composite_common.h's sigmoidf
 __device__ __forceinline__ float march_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }
 
+// kSlab: one slab of a march in slabs (the state, first and last of the arguments), else the whole list
+template <bool kSlab>
 __global__ void __launch_bounds__(kMarchThreads) march_composite_kernel(MarchCompositeArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
@@ -189,6 +231,11 @@ __global__ void __launch_bounds__(kMarchThreads) march_composite_kernel(MarchCom
     end = end < 0 ? 0 : (end > a.n ? a.n : end);
     beg = beg < 0 ? 0 : (beg > end ? end : beg);
     double carry = 1.0, r0 = 0, r1 = 0, r2 = 0, acc = 0, dn = 0;
+    if (kSlab && !a.first) {   // the earlier slabs' sums join lane 0's
+        const double* st = a.state + 6 * r;
+        carry = st[0];
+        if (lane == 0) { r0 = st[1]; r1 = st[2]; r2 = st[3]; acc = st[4]; dn = st[5]; }
+    }
     for (int64_t j0 = beg; j0 < end; j0 += 64) {
         const int64_t j = j0 + lane;
         float c0 = 0.f, c1 = 0.f, c2 = 0.f, zj = 0.f, alpha = 0.f, t = 1.f;
@@ -214,9 +261,18 @@ __global__ void __launch_bounds__(kMarchThreads) march_composite_kernel(MarchCom
         dn += (double)(w * zj);
         if (a.weights && j < end) a.weights[j] = w;
     }
-    float rgb0 = (float)wave_sum_dpp(r0), rgb1 = (float)wave_sum_dpp(r1), rgb2 = (float)wave_sum_dpp(r2);
-    const float facc = (float)wave_sum_dpp(acc);
-    const float num = (float)wave_sum_dpp(dn);
+    const double s0 = wave_sum_dpp(r0), s1 = wave_sum_dpp(r1), s2 = wave_sum_dpp(r2), sa = wave_sum_dpp(acc),
+                 sn = wave_sum_dpp(dn);
+    if (kSlab && !a.last) {
+        if (lane == 0) {
+            double* st = a.state + 6 * r;
+            st[0] = carry; st[1] = s0; st[2] = s1; st[3] = s2; st[4] = sa; st[5] = sn;
+        }
+        return;
+    }
+    float rgb0 = (float)s0, rgb1 = (float)s1, rgb2 = (float)s2;
+    const float facc = (float)sa;
+    const float num = (float)sn;
     if (lane == 0) {
         const float depth = num / facc;   // NaN at 0 / 0, as ray_sums
         const float mx = (depth != depth) ? depth : fmaxf(1e-10f, depth);
@@ -231,9 +287,38 @@ __global__ void __launch_bounds__(kMarchThreads) march_composite_kernel(MarchCom
     }
 }
 
+// ---------------------------------------------------------------- the stopping rule
+// one thread per ray over its segment of the slab's list: early_stop.hip's ert_advance_kernel on packed entries
+__global__ void __launch_bounds__(256) march_advance_kernel(const float* __restrict__ raw, const float* __restrict__ dist,
+                                                            const int32_t* __restrict__ off,
+                                                            const float* __restrict__ rays_d, int64_t R, int64_t n,
+                                                            int s1, float tau_max, float* __restrict__ tau,
+                                                            uint8_t* __restrict__ alive, int32_t* __restrict__ stop) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R || !alive[r]) return;
+    const float dx = rays_d[3 * r + 0], dy = rays_d[3 * r + 1], dz = rays_d[3 * r + 2];
+    const float norm_d = sqrtf(dx * dx + dy * dy + dz * dz);
+    // the segment, held inside the list whatever the offsets say
+    int64_t end = off[r + 1], beg = off[r];
+    end = end < 0 ? 0 : (end > n ? n : end);
+    beg = beg < 0 ? 0 : (beg > end ? end : beg);
+    float t = tau[r];
+    for (int64_t e = beg; e < end; ++e) {
+        const float d = dist[e] * norm_d;
+        const float sg = raw[4 * e + 3];
+        const float s = sg > 0.f ? sg : 0.f;
+        t = t + s * d;
+    }
+    tau[r] = t;
+    if (t > tau_max) {
+        alive[r] = 0;
+        stop[r] = s1;
+    }
+}
+
 // the checks the count and the write entries share
-static int march_args(MarchArgs& a, const char* what, int64_t n_rays, int n_cols, int64_t n_samples,
-                      const float* bmin, const float* bmax, int res, bool needs_ws, void* d_workspace,
+static int march_args(MarchArgs& a, const char* what, int64_t n_rays, int n_cols, int64_t n_samples, int64_t k0,
+                      int64_t k1, const float* bmin, const float* bmax, int res, bool needs_ws, void* d_workspace,
                       size_t workspace_bytes) {
     int rc = fill_grid(a.g, bmin, bmax, res);
     if (rc) return rc;
@@ -246,7 +331,9 @@ static int march_args(MarchArgs& a, const char* what, int64_t n_rays, int n_cols
     const size_t need = compact_workspace_bytes(n_rays);
     NERF_REQUIRE(!needs_ws || n_rays == 0 || (d_workspace && workspace_bytes >= need),
                  "%s: null workspace, or workspace %zu B < %zu B", what, workspace_bytes, need);
-    a.R = n_rays; a.C = n_cols; a.K = (int)n_samples;
+    NERF_REQUIRE(k0 >= 0 && k0 <= k1 && k1 <= n_samples, "%s: lattice range [%lld, %lld) of %lld samples", what,
+                 (long long)k0, (long long)k1, (long long)n_samples);
+    a.R = n_rays; a.C = n_cols; a.K = (int)n_samples; a.k0 = (int)k0; a.k1 = (int)k1;
     a.block_counts = needs_ws ? static_cast<int32_t*>(d_workspace) : nullptr;
     return NERF_OK;
 }
@@ -257,26 +344,70 @@ using namespace nerf;
 
 extern "C" size_t nerf_march_workspace_bytes(int64_t n_rays) { return compact_workspace_bytes(n_rays); }
 
+// nerf_march_count (0, K, NULL) and nerf_slab_march_count
+static int march_count(const char* what, const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                       int64_t n_samples, int64_t k0, int64_t k1, const uint8_t* d_alive, const float* bbox_min,
+                       const float* bbox_max, int res, const uint32_t* d_bits, int32_t* d_counts, int32_t* d_offsets,
+                       float* d_rays_d, void* d_workspace, size_t workspace_bytes, void* stream) {
+    MarchArgs a{};
+    int rc = march_args(a, what, n_rays, n_cols, n_samples, k0, k1, bbox_min, bbox_max, res, true, d_workspace,
+                        workspace_bytes);
+    if (rc) return rc;
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets, "%s: null arg", what);
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = d_counts; a.off = d_offsets; a.rays_d = d_rays_d;
+    a.alive = d_alive;
+    hipLaunchKernelGGL(march_count_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+                       as_stream(stream), a);
+    const dim3 scan_grid(blocks_for(n_rays, kCompactBlock));
+    hipLaunchKernelGGL(march_block_counts_kernel, scan_grid, dim3(kCompactThreads), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(march_offsets_kernel, scan_grid, dim3(kCompactThreads), 0, as_stream(stream), a);
+    NERF_CHECK_LAUNCH(what);
+    return NERF_OK;
+}
+
 extern "C" int nerf_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
                                 const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
                                 int32_t* d_counts, int32_t* d_offsets, float* d_rays_d, void* d_workspace,
                                 size_t workspace_bytes, void* stream) {
+    // an n_samples the checks refuse gives the range [0, 0), so that they refuse n_samples and not the range
+    return march_count("march_count", d_rays, n_rays, n_cols, d_t, n_samples, 0, n_samples > 0 ? n_samples : 0, nullptr,
+                       bbox_min, bbox_max, res, d_bits, d_counts, d_offsets, d_rays_d, d_workspace, workspace_bytes,
+                       stream);
+}
+
+extern "C" int nerf_slab_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                     int64_t n_samples, int64_t k0, int64_t k1, const uint8_t* d_alive,
+                                     const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                                     int32_t* d_counts, int32_t* d_offsets, float* d_rays_d, void* d_workspace,
+                                     size_t workspace_bytes, void* stream) {
+    return march_count("slab_march_count", d_rays, n_rays, n_cols, d_t, n_samples, k0, k1, d_alive, bbox_min, bbox_max,
+                       res, d_bits, d_counts, d_offsets, d_rays_d, d_workspace, workspace_bytes, stream);
+}
+
+// nerf_march_write (0, K) and nerf_slab_march_write; the write needs no alive flags: a dead ray's count is 0
+static int march_write(const char* what, const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                       int64_t n_samples, int64_t k0, int64_t k1, const float* bbox_min, const float* bbox_max, int res,
+                       const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points,
+                       int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
     MarchArgs a{};
-    int rc = march_args(a, "march_count", n_rays, n_cols, n_samples, bbox_min, bbox_max, res, true, d_workspace,
-                        workspace_bytes);
+    int rc = march_args(a, what, n_rays, n_cols, n_samples, k0, k1, bbox_min, bbox_max, res, false, nullptr, 0);
     if (rc) return rc;
-    if (n_rays == 0) return NERF_OK;
-    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets, "march_count: null arg");
-    if (hipMemsetAsync(d_workspace, 0, compact_workspace_bytes(n_rays), as_stream(stream)) != hipSuccess) {
-        set_error("march_count: hipMemsetAsync failed");
-        return NERF_E_LAUNCH;
-    }
-    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = d_counts; a.off = d_offsets; a.rays_d = d_rays_d;
-    hipLaunchKernelGGL(march_count_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+    NERF_REQUIRE(n_points >= 0 && n_points <= n_rays * (k1 - k0), "%s: count %lld of %lld lattice samples", what,
+                 (long long)n_points, (long long)(n_rays * (k1 - k0)));
+    NERF_REQUIRE(capacity >= n_points, "%s: capacity %lld below the count %lld", what, (long long)capacity,
+                 (long long)n_points);
+    if (n_rays == 0 || n_points == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets && d_pts_c && d_z_c && d_dist_c, "%s: null arg",
+                 what);
+    NERF_REQUIRE(!d_sh_c || (n_cols == 11 && ((uintptr_t)d_sh_c & 15) == 0),
+                 "%s: SH rows need ray rows of 11 columns and a 16-B aligned sh_c", what);
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = const_cast<int32_t*>(d_counts);
+    a.off = const_cast<int32_t*>(d_offsets);
+    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c;
+    hipLaunchKernelGGL(march_write_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
                        as_stream(stream), a);
-    hipLaunchKernelGGL(march_offsets_kernel, dim3(blocks_for(n_rays, kCompactBlock)), dim3(kCompactThreads), 0,
-                       as_stream(stream), a);
-    NERF_CHECK_LAUNCH("march_count");
+    NERF_CHECK_LAUNCH(what);
     return NERF_OK;
 }
 
@@ -284,24 +415,49 @@ extern "C" int nerf_march_write(const float* d_rays, int64_t n_rays, int n_cols,
                                 const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
                                 const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points, int64_t capacity,
                                 float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
-    MarchArgs a{};
-    int rc = march_args(a, "march_write", n_rays, n_cols, n_samples, bbox_min, bbox_max, res, false, nullptr, 0);
+    return march_write("march_write", d_rays, n_rays, n_cols, d_t, n_samples, 0, n_samples > 0 ? n_samples : 0, bbox_min,
+                       bbox_max, res, d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, d_sh_c,
+                       stream);
+}
+
+extern "C" int nerf_slab_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                     int64_t n_samples, int64_t k0, int64_t k1, const float* bbox_min,
+                                     const float* bbox_max, int res, const uint32_t* d_bits, const int32_t* d_counts,
+                                     const int32_t* d_offsets, int64_t n_points, int64_t capacity, float* d_pts_c,
+                                     float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
+    return march_write("slab_march_write", d_rays, n_rays, n_cols, d_t, n_samples, k0, k1, bbox_min, bbox_max, res,
+                       d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, d_sh_c, stream);
+}
+
+// the checks the two compositing entries and the stopping rule share: the sizes and the packed list
+static int march_list_args(const char* what, int64_t n_rays, int64_t n_points) {
+    NERF_REQUIRE(n_rays >= 0 && n_rays <= INT32_MAX, "%s: n_rays %lld", what, (long long)n_rays);
+    NERF_REQUIRE(n_points >= 0 && n_points <= INT32_MAX && n_points <= n_rays * kMarchMaxSamples,
+                 "%s: n_points %lld of %lld rays (at most %d each)", what, (long long)n_points, (long long)n_rays,
+                 kMarchMaxSamples);
+    return NERF_OK;
+}
+
+// nerf_march_composite (state NULL: the whole list) and nerf_slab_march_composite
+static int march_composite(const char* what, const float* d_raw, const float* d_z, const float* d_dist,
+                           const int32_t* d_offsets, const float* d_rays_d, int64_t n_rays, int64_t n_points,
+                           int white_bkgd, bool slab, double* d_state, int first, int last, float* d_rgb, float* d_disp,
+                           float* d_acc, float* d_depth, float* d_weights, void* stream) {
+    int rc = march_list_args(what, n_rays, n_points);
     if (rc) return rc;
-    NERF_REQUIRE(n_points >= 0 && n_points <= n_rays * n_samples, "march_write: count %lld of %lld lattice samples",
-                 (long long)n_points, (long long)(n_rays * n_samples));
-    NERF_REQUIRE(capacity >= n_points, "march_write: capacity %lld below the count %lld", (long long)capacity,
-                 (long long)n_points);
-    if (n_rays == 0 || n_points == 0) return NERF_OK;
-    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets && d_pts_c && d_z_c && d_dist_c,
-                 "march_write: null arg");
-    NERF_REQUIRE(!d_sh_c || (n_cols == 11 && ((uintptr_t)d_sh_c & 15) == 0),
-                 "march_write: SH rows need ray rows of 11 columns and a 16-B aligned sh_c");
-    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = const_cast<int32_t*>(d_counts);
-    a.off = const_cast<int32_t*>(d_offsets);
-    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c;
-    hipLaunchKernelGGL(march_write_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
-                       as_stream(stream), a);
-    NERF_CHECK_LAUNCH("march_write");
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_offsets && d_rays_d && d_rgb && d_acc && d_depth, "%s: null arg", what);
+    NERF_REQUIRE(!slab || d_state, "%s: null state", what);
+    NERF_REQUIRE(n_points == 0 || (d_raw && d_z && d_dist && ((uintptr_t)d_raw & 15) == 0),
+                 "%s: null arg, or raw rows not 16-B aligned", what);
+    MarchCompositeArgs a{};
+    a.raw = d_raw; a.z = d_z; a.dist = d_dist; a.off = d_offsets; a.rays_d = d_rays_d; a.R = n_rays; a.n = n_points;
+    a.white = white_bkgd ? 1 : 0; a.rgb = d_rgb; a.disp = d_disp; a.acc = d_acc; a.depth = d_depth;
+    a.weights = d_weights; a.state = d_state; a.first = first ? 1 : 0; a.last = last ? 1 : 0;
+    const dim3 grid(blocks_for(n_rays, kMarchWaves)), block(kMarchThreads);
+    if (slab) hipLaunchKernelGGL(march_composite_kernel<true>, grid, block, 0, as_stream(stream), a);
+    else hipLaunchKernelGGL(march_composite_kernel<false>, grid, block, 0, as_stream(stream), a);
+    NERF_CHECK_LAUNCH(what);
     return NERF_OK;
 }
 
@@ -309,20 +465,32 @@ extern "C" int nerf_march_composite(const float* d_raw, const float* d_z, const 
                                     const int32_t* d_offsets, const float* d_rays_d, int64_t n_rays, int64_t n_points,
                                     int white_bkgd, float* d_rgb, float* d_disp, float* d_acc, float* d_depth,
                                     float* d_weights, void* stream) {
-    NERF_REQUIRE(n_rays >= 0 && n_rays <= INT32_MAX, "march_composite: n_rays %lld", (long long)n_rays);
-    NERF_REQUIRE(n_points >= 0 && n_points <= INT32_MAX && n_points <= n_rays * kMarchMaxSamples,
-                 "march_composite: n_points %lld of %lld rays (at most %d each)", (long long)n_points,
-                 (long long)n_rays, kMarchMaxSamples);
+    return march_composite("march_composite", d_raw, d_z, d_dist, d_offsets, d_rays_d, n_rays, n_points, white_bkgd,
+                           false, nullptr, 1, 1, d_rgb, d_disp, d_acc, d_depth, d_weights, stream);
+}
+
+extern "C" int nerf_slab_march_composite(const float* d_raw, const float* d_z, const float* d_dist,
+                                         const int32_t* d_offsets, const float* d_rays_d, int64_t n_rays,
+                                         int64_t n_points, int white_bkgd, double* d_state, int first, int last,
+                                         float* d_rgb, float* d_disp, float* d_acc, float* d_depth, float* d_weights,
+                                         void* stream) {
+    return march_composite("slab_march_composite", d_raw, d_z, d_dist, d_offsets, d_rays_d, n_rays, n_points,
+                           white_bkgd, true, d_state, first, last, d_rgb, d_disp, d_acc, d_depth, d_weights, stream);
+}
+
+extern "C" int nerf_slab_march_advance(const float* d_raw, const float* d_dist, const int32_t* d_offsets,
+                                       const float* d_rays_d, int64_t n_rays, int64_t n_points, int64_t s1,
+                                       float tau_max, float* d_tau, uint8_t* d_alive, int32_t* d_stop, void* stream) {
+    int rc = march_list_args("slab_march_advance", n_rays, n_points);
+    if (rc) return rc;
+    NERF_REQUIRE(s1 >= 0 && s1 <= kMarchMaxSamples, "slab_march_advance: slab end %lld (0..%d)", (long long)s1,
+                 kMarchMaxSamples);
+    NERF_REQUIRE(tau_max > 0.f, "slab_march_advance: tau_max %g must be positive", (double)tau_max);
     if (n_rays == 0) return NERF_OK;
-    NERF_REQUIRE(d_offsets && d_rays_d && d_rgb && d_acc && d_depth, "march_composite: null arg");
-    NERF_REQUIRE(n_points == 0 || (d_raw && d_z && d_dist && ((uintptr_t)d_raw & 15) == 0),
-                 "march_composite: null arg, or raw rows not 16-B aligned");
-    MarchCompositeArgs a{};
-    a.raw = d_raw; a.z = d_z; a.dist = d_dist; a.off = d_offsets; a.rays_d = d_rays_d; a.R = n_rays; a.n = n_points;
-    a.white = white_bkgd ? 1 : 0; a.rgb = d_rgb; a.disp = d_disp; a.acc = d_acc; a.depth = d_depth;
-    a.weights = d_weights;
-    hipLaunchKernelGGL(march_composite_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
-                       as_stream(stream), a);
-    NERF_CHECK_LAUNCH("march_composite");
+    NERF_REQUIRE(d_offsets && d_rays_d && d_tau && d_alive && d_stop, "slab_march_advance: null arg");
+    NERF_REQUIRE(n_points == 0 || (d_raw && d_dist), "slab_march_advance: null arg");
+    hipLaunchKernelGGL(march_advance_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, as_stream(stream), d_raw,
+                       d_dist, d_offsets, d_rays_d, n_rays, n_points, (int)s1, tau_max, d_tau, d_alive, d_stop);
+    NERF_CHECK_LAUNCH("slab_march_advance");
     return NERF_OK;
 }

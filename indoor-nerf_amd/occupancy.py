@@ -220,8 +220,10 @@ class OccupancyGrid:
         return hit, span, rows, rays_c
 
     # ---- grid ray marching (csrc/march.hip) ----------------------------------------
-    def _march_count(self, rays, K):
-        """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n)."""
+    def _march_count(self, rays, K, k0=None, k1=None, alive=None, dirs=True):
+        """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n). With a
+        lattice range [k0, k1) (and alive, uint8 [R], or None for every ray): nerf_slab_march_count over that range
+        of the rays alive. dirs=False: rays_d is not written (None)."""
         from .render import _linspace
         rays = _packed_rows(rays, "march")
         K = check_march_samples(K, "OccupancyGrid.march")
@@ -231,24 +233,29 @@ class OccupancyGrid:
         i32 = dict(device=dev, dtype=torch.int32)
         t = _linspace(K, dev)
         counts, offsets = torch.empty(R, **i32), torch.zeros(R + 1, **i32) if R == 0 else torch.empty(R + 1, **i32)
-        rays_d = torch.empty(R, 3, device=dev, dtype=torch.float32)
+        rays_d = torch.empty(R, 3, device=dev, dtype=torch.float32) if dirs else None
         n = 0
         if R > 0:
             ws = torch.empty(int(_lib.load().nerf_march_workspace_bytes(R)) // 4, **i32)
-            _lib.call("nerf_march_count", _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, self._bmin, self._bmax,
+            name, slab = "nerf_march_count", ()
+            if k0 is not None:
+                name, slab = "nerf_slab_march_count", (int(k0), int(k1), _lib.ptr(alive, "alive", torch.uint8, True))
+            _lib.call(name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab, self._bmin, self._bmax,
                       self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
-                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"),
+                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d", allow_none=True),
                       _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
             n = int(offsets[R].item())     # one 4-byte host read sizes the list
         return rays, t, counts, offsets, rays_d, n
 
-    def _march_write(self, rays, t, K, counts, offsets, n, sh):
+    def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None):
+        """nerf_march_write of the list _march_count sized; with the same [k0, k1): nerf_slab_march_write."""
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
         f = dict(device=dev, dtype=torch.float32)
         pts_c, z_c, dist_c = torch.empty(n, 3, **f), torch.empty(n, **f), torch.empty(n, **f)
         sh_c = torch.empty(n, 16, **f) if sh else None
         if n > 0:
-            _lib.call("nerf_march_write", _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, self._bmin, self._bmax,
+            name, slab = ("nerf_march_write", ()) if k0 is None else ("nerf_slab_march_write", (int(k0), int(k1)))
+            _lib.call(name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab, self._bmin, self._bmax,
                       self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
                       _lib.ptr(offsets, "offsets", torch.int32), n, n, _lib.ptr(pts_c, "pts_c"), _lib.ptr(z_c, "z_c"),
                       _lib.ptr(dist_c, "dist_c"), _lib.ptr(sh_c, "sh_c", allow_none=True), _lib.stream())

@@ -430,7 +430,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
-                table_precision=None):
+                table_precision=None, march_stop=None, march_stop_slab=128):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -456,7 +456,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     launch of the call gather from an fp16 image of the tables (HashEmbedder.half_tables, nerf_hash_encode_fwd_half):
     each table value rounded once to binary16, everything else unchanged, so the result is bit for bit the default
     render of a model whose tables are t.half().float(). Composes with occupancy=, early_stop=, march= and
-    mlp_precision=. None and "fp32" are the call without it."""
+    mlp_precision=. None and "fp32" are the call without it.
+    march_stop (a float transmittance threshold 0 < eps < 1; with march=): the march runs front to back
+    in slabs of march_stop_slab lattice samples, and a ray whose optical depth over the samples evaluated so far has
+    passed -log(eps) after a slab is not walked in any later slab. The result is the march with sigma masked by
+    k < march_stop_samples[r] (int32 [R]: the slab boundary at which the ray stopped, march_samples if it never
+    did); march_samples then counts the samples actually evaluated. Each map differs from the unstopped march's by
+    at most eps. With retraw the packed entries come per slab: march_slabs, a list of (offsets, raw, pts, z_vals).
+    Composes with mlp_precision=, table_precision= and render's ray_bounds=. None (the default) is the march
+    without it: no other launch, no other buffer."""
     half = False
     if table_precision is not None:
         from .sparse_field import check_table_nets, check_table_precision
@@ -469,12 +477,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         bf16 = check_mlp_precision(mlp_precision, "render_rays")
     if bf16:
         check_mlp_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn, predict_normals)
+    if march_stop is not None and march is None:
+        from .sparse_field import check_march_stop
+        check_march_stop(march_stop, march_stop_slab, march, "render_rays")
     if march is not None:
         return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points,
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  bf16=bf16, half=half)
+                                  bf16=bf16, half=half, march_stop=march_stop, march_stop_slab=march_stop_slab)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -591,10 +602,11 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
 
 
 def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, perturb, raw_noise_std, predict_normals,
-                 occupancy, early_stop):
-    """render_rays' refusals with march=, all before any launch."""
+                 occupancy, early_stop, march_stop=None, march_stop_slab=128):
+    """render_rays' refusals with march=, all before any launch -> (K, (eps, slab) of march_stop or None)."""
     from .occupancy import OccupancyGrid, _check_modules, check_march_samples
-    from .sparse_field import check_forward_only, check_march_points
+    from .sparse_field import check_forward_only, check_march_points, check_march_stop
+    stop = check_march_stop(march_stop, march_stop_slab, grid, "render_rays")
     if not isinstance(grid, OccupancyGrid):
         raise ValueError(f"render_rays: march must be an OccupancyGrid, got {type(grid).__name__}")
     K = check_march_samples(march_samples, "render_rays: march")
@@ -611,33 +623,43 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
         raise ValueError("render_rays: march does not support predict_normals or a normals head")
     if embed_fn is not None:
         _check_modules(embed_fn, fn, "render_rays: march")
-    return K
+    return K, stop
 
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False):
+                       predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False,
+                       march_stop=None, march_stop_slab=128):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
-    the list (sparse_field.run_network_packed), the packed compositing."""
+    the list (sparse_field.run_network_packed), the packed compositing. With march_stop the same in slabs
+    (_march_slabs)."""
     run_fn = network_fn if network_fine is None else network_fine
-    K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
-                     predict_normals, occupancy, early_stop)
+    K, stop = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
+                           predict_normals, occupancy, early_stop, march_stop, march_stop_slab)
     if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
         raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
-    from .sparse_field import MarchRequest
-    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K)
-    R, dev = rays.shape[0], rays.device
-    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True)
-    grid._last = (n, R * K)
-    f = dict(device=dev, dtype=torch.float32)
-    if n > 0:
+
+    def field(rays, pts_c, sh_c):
+        """The field on a packed list of n > 0 points."""
+        from .sparse_field import MarchRequest
         req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
         raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half)
         del pts_c._nerf_sparse
         if not req.used:   # a foreign query function ignores the attribute: never fall back silently
             raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
-    else:
-        raw = torch.empty(0, 4, **f)
+        return raw
+
+    if stop is not None:
+        ret = _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw)
+        if DEBUG:
+            check_numerics(ret)
+        return ret
+    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K)
+    R, dev = rays.shape[0], rays.device
+    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True)
+    grid._last = (n, R * K)
+    f = dict(device=dev, dtype=torch.float32)
+    raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
     rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
     if R > 0:
         _lib.call("nerf_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z_c, "z_c"), _lib.ptr(dist_c, "dist_c"),
@@ -650,6 +672,61 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
         ret.update(raw=raw, pts=pts_c, z_vals=z_c, march_offsets=offsets)
     if DEBUG:
         check_numerics(ret)
+    return ret
+
+
+def _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw):
+    """The march of _render_rays_march with march_stop = stop = (eps, slab): the lattice front to
+    back in slabs; per slab the packed list of the rays alive (one 4-byte host read sizes it), field(rays, pts_c,
+    sh_c) on it, its compositing into the per-ray state and, unless it is the last, the stopping rule. A slab with
+    an empty list skips the field and its launches (the last slab's compositing always runs: it writes the maps)."""
+    from .early_stop import tau_max_of
+    eps, Ks = stop
+    tau_max = tau_max_of(eps)
+    rays = tau = alive = stops = state = rays_d = None
+    rgb_map = depth_map = acc_map = None
+    slabs, counts_all, evaluated, first = [], [], 0, True
+    for k0 in range(0, K, Ks):
+        k1 = min(k0 + Ks, K)
+        rays, t, counts, offsets, dirs, n = grid._march_count(ray_batch if rays is None else rays, K, k0, k1, alive,
+                                                              dirs=rays_d is None)
+        R, dev = rays.shape[0], rays.device
+        f = dict(device=dev, dtype=torch.float32)
+        if rays_d is None:      # slab 0: the state every later slab carries
+            rays_d = dirs
+            rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
+            if k1 < K:
+                tau, alive = torch.zeros(R, **f), torch.ones(R, device=dev, dtype=torch.uint8)
+                state = torch.empty(R, 6, device=dev, dtype=torch.float64)
+            stops = torch.full((R,), K, device=dev, dtype=torch.int32)
+        pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, k0, k1)
+        raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
+        evaluated += n
+        counts_all.append(counts)
+        if retraw:
+            slabs.append((offsets, raw, pts_c, z_c))
+        last = k1 == K
+        if R > 0 and (n > 0 or last):
+            if state is None:   # one slab: no state to carry
+                state = torch.empty(R, 6, device=dev, dtype=torch.float64)
+            _lib.call("nerf_slab_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z_c, "z_c"), _lib.ptr(dist_c, "dist_c"),
+                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n,
+                      int(bool(white_bkgd)), _lib.ptr(state, "state", torch.float64), int(first), int(last),
+                      _lib.ptr(rgb_map, "rgb"), None, _lib.ptr(acc_map, "acc"), _lib.ptr(depth_map, "depth"), None,
+                      _lib.stream())
+            first = False
+        if R > 0 and n > 0 and not last:
+            _lib.call("nerf_slab_march_advance", _lib.ptr(raw, "raw"), _lib.ptr(dist_c, "dist_c"),
+                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n, k1, tau_max,
+                      _lib.ptr(tau, "tau"), _lib.ptr(alive, "alive", torch.uint8), _lib.ptr(stops, "stop", torch.int32),
+                      _lib.stream())
+    grid._last = (evaluated, rays.shape[0] * K)
+    total = counts_all[0] if len(counts_all) == 1 else torch.stack(counts_all).sum(0, dtype=torch.int32)
+    # restated for zero rays in _no_rays_result: keep the two in step
+    ret = dict(rgb_map=rgb_map, depth_map=depth_map, acc_map=acc_map, march_samples=total, rays_d=rays_d,
+               march_stop_samples=stops)
+    if retraw:
+        ret["march_slabs"] = slabs
     return ret
 
 
@@ -741,12 +818,15 @@ def _missed_value(key, white_bkgd):
 
 
 def _no_rays_result(device, N_samples, N_importance=0, retraw=False, predict_normals=False, early_stop=None,
-                    network_fn=None, network_fine=None, march=None, **_):
+                    network_fn=None, network_fine=None, march=None, march_stop=None, **_):
     """render_rays' result for zero rays, without a field call (every ray of the frame missed)."""
     f = dict(device=device, dtype=torch.float32)
     if march is not None:   # _render_rays_march's entries (render() refuses retraw with march)
-        return dict(rgb_map=torch.empty(0, 3, **f), depth_map=torch.empty(0, **f), acc_map=torch.empty(0, **f),
-                    march_samples=torch.empty(0, device=device, dtype=torch.int32), rays_d=torch.empty(0, 3, **f))
+        ret = dict(rgb_map=torch.empty(0, 3, **f), depth_map=torch.empty(0, **f), acc_map=torch.empty(0, **f),
+                   march_samples=torch.empty(0, device=device, dtype=torch.int32), rays_d=torch.empty(0, 3, **f))
+        if march_stop is not None:
+            ret["march_stop_samples"] = torch.empty(0, device=device, dtype=torch.int32)
+        return ret
     M = N_samples + N_importance
     fine = network_fn if network_fine is None else network_fine
     ret = {}
@@ -794,7 +874,9 @@ def _render_bounded(rays, chunk, grid, kwargs):
         idx = rows.long()
         all_ret = {}
         for k, v in part.items():
-            full = torch.full((R,) + tuple(v.shape[1:]), _missed_value(k, white), device=v.device, dtype=v.dtype)
+            # a missed ray never stopped: its march_stop_samples is the lattice's length
+            fill = kwargs.get("march_samples", 512) if k == "march_stop_samples" else _missed_value(k, white)
+            full = torch.full((R,) + tuple(v.shape[1:]), fill, device=v.device, dtype=v.dtype)
             all_ret[k] = full.index_copy_(0, idx, v)
     all_ret.update(ray_hit=hit, ray_span=span)
     return all_ret
@@ -810,7 +892,11 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     default) leaves the call as it is without it.
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
     spans its own [near', far']. mlp_precision and table_precision go to
-    render_rays as well. retraw is refused with march: the packed entries of several chunks do not concatenate."""
+    render_rays as well, and so do march_stop and march_stop_slab. retraw is refused with march: the
+    packed entries of several chunks do not concatenate."""
+    if kwargs.get("march_stop") is not None:   # also when no chunk reaches render_rays
+        from .sparse_field import check_march_stop
+        check_march_stop(kwargs["march_stop"], kwargs.get("march_stop_slab", 128), kwargs.get("march"), "render")
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")

@@ -7,6 +7,7 @@ the call to run_network_sparse. The kept samples are compacted in ascending orde
 (csrc/sparse_points.hip), hash-encoded and run through the MLP, whose results land in their rows of raw;
 every other sample gets an all-zero raw row, which compositing gives weight 0 exactly.
 """
+import numpy as np
 import torch
 
 from . import _lib
@@ -163,6 +164,22 @@ def check_march_points(m):
     if 16 * (m + 32) >= 2 ** 31:
         raise ValueError(f"march: march_points {m} exceeds the MLP's 32-bit row indexing (16 (n + 32) < 2^31)")
     return m
+
+
+def check_march_stop(march_stop, march_stop_slab, march, prefix):
+    """march_stop / march_stop_slab of `prefix` (render_rays, render) -> (eps, slab), or None without march_stop;
+    their refusals, one fixed sentence each."""
+    if march_stop is None:
+        return None
+    if march is None:
+        raise ValueError(f"{prefix}: march_stop needs march= (rays are stopped inside a grid march; early_stop= is the "
+                         "dense path's)")
+    if isinstance(march_stop, bool) or not isinstance(march_stop, (float, np.floating)) or not 0.0 < march_stop < 1.0:
+        raise ValueError(f"{prefix}: march_stop must be a float transmittance threshold in (0, 1), got {march_stop!r}")
+    if (isinstance(march_stop_slab, bool) or not isinstance(march_stop_slab, (int, np.integer))
+            or march_stop_slab < 1):
+        raise ValueError(f"{prefix}: march_stop_slab must be a positive integer, got {march_stop_slab!r}")
+    return float(march_stop), int(march_stop_slab)
 
 
 def check_forward_only(what, prefix, raw_noise_std=0.):

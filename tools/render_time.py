@@ -43,12 +43,25 @@ both mlp_precision settings. Per variant: the frame time and its ratio to the fp
 target, the PSNR of the fp16-table frame against its fp32-table twin, and from one extra frame with a pair of device
 events around every launch the time of the hash-encoding launches and their share of all launches' time.
 
+With --march-stop the same frame, process and method time stopping opaque rays inside the march instead
+(render(march=grid, march_stop=eps), csrc/march.hip nerf_slab_march_*): through the scene's own geometry
+grid and the grid of update()'s defaults, at 192 and 512 lattice samples per ray, the march without stop (the parent
+path: the comparison for every ratio), march_stop in {1e-2, 1e-3} x march_stop_slab in {32, 64, 128}, and per slab size
+march_stop=1e-300, at which nothing terminates (the cost of the slabs alone). Per variant: the points the field
+evaluated, the share of rays stopped, the frame time and its ratio to the unstopped twin's, the PSNR against the target
+and against the unstopped twin; for the unstopped rows and the 1e-300 rows also the time of every launch from one extra
+frame with a pair of device events around each. --iters sets the training iterations of the scene (300: the hazy scene of the other
+tables); --opaque-curve 300,1000,... trains the scene afresh at each count in turn, records the dense PSNR and runs the
+table at the first count after which the dense PSNR rises by less than 0.1 dB (the last count if none).
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
        python tools/render_time.py --march [--out profiles/march_render_time.json]
        python tools/render_time.py --mlp-precision [--out profiles/mlp_bf16_render_time.json]
        python tools/render_time.py --table-precision [--out profiles/table_fp16_render_time.json]
+       python tools/render_time.py --march-stop [--iters 300 | --opaque-curve 300,1000,2000,4000]
+                                                [--out profiles/march_stop_render_time.json]
 """
 import argparse
 import json
@@ -400,6 +413,77 @@ def main_table_precision(a):
                                                 "default grid": default.occupied_fraction()})
 
 
+def opaque_setup(a, counts):
+    """The scene trained afresh at each of `counts` in turn until the dense PSNR of the frame stops rising:
+    (setup() of the chosen count, {count: dense PSNR})."""
+    curve, prev = {}, None
+    for c in counts:
+        a.iters = c
+        s = setup(a)
+        curve[c] = s.psnr(s.frame({})[0])
+        print(f"march-stop: {c} iterations, dense PSNR {curve[c]:.3f} dB", flush=True)
+        if prev is not None and curve[c] - curve[prev[0]] < 0.1:
+            a.iters = prev[0]
+            return prev[1], curve
+        prev = (c, s)
+    return prev[1], curve
+
+
+def main_march_stop(a):
+    """The march_stop table: see the module docstring."""
+    curve = None
+    if a.opaque_curve:
+        s, curve = opaque_setup(a, [int(c) for c in a.opaque_curve.split(",")])
+    else:
+        s = setup(a)
+    grids = {f"{kind} grid": s.new_grid(kind) for kind in ("geometry", "default")}
+    variants, twin, desc = [("dense", {})], {}, {"dense": {}}
+    for gname, grid in grids.items():
+        for K in (192, 512):
+            base = f"{gname}: march, K = {K}"
+            over = dict(march=grid, march_samples=K)
+            variants.append((base, over))
+            desc[base] = dict(grid=gname, march_samples=K, march_stop=None, march_stop_slab=None)
+            for eps in (1e-2, 1e-3, 1e-300):
+                for slab in (32, 64, 128):
+                    name = f"{base}, stop {eps:g}, slab {slab}"
+                    variants.append((name, dict(over, march_stop=eps, march_stop_slab=slab)))
+                    twin[name] = base
+                    desc[name] = dict(grid=gname, march_samples=K, march_stop=eps, march_stop_slab=slab)
+
+    report, images = {}, {}
+    for name, over in variants:         # one untimed frame per variant: PSNR, evaluated points, rays stopped
+        out = s.frame(over)
+        images[name] = out[0]
+        report[name] = dict(desc[name], psnr_db=s.psnr(out[0]))
+        if "march" in over:
+            K = over["march_samples"]
+            n = int(out[3]["march_samples"].sum())
+            report[name].update(evaluated_points=n, lattice_points=s.H * s.W * K, share=n / (s.H * s.W * K))
+        if name in twin:
+            K = over["march_samples"]
+            d = (images[name] - images[twin[name]]).double()
+            mse = float((d ** 2).mean())
+            report[name].update(rays_stopped_share=float((out[3]["march_stop_samples"] < K).float().mean()),
+                                slabs=-(-K // over["march_stop_slab"]),
+                                psnr_vs_unstopped_twin_db=float("inf") if mse == 0 else -10.0 * float(np.log10(mse)),
+                                max_abs_rgb_diff_vs_unstopped_twin=float(d.abs().max()),
+                                evaluated_over_unstopped_twin=report[name]["evaluated_points"]
+                                / max(1, report[twin[name]]["evaluated_points"]))
+    for name, over in variants:         # where the launches' time goes: the unstopped rows and their pure-overhead twins
+        if "march" in over and over.get("march_stop") in (None, 1e-300):
+            ms = launch_times(s, over)
+            report[name].update(all_launches_ms=sum(ms.values()),
+                                launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_unstopped_twin"] = float(np.median(times[name]) / np.median(times[base]))
+        report[name]["ms_per_extra_slab_vs_unstopped_twin"] = float(
+            (np.median(times[name]) - np.median(times[base])) / max(1, report[name]["slabs"] - 1))
+    write(a, s, report, grid_occupied_fraction={k: g.occupied_fraction() for k, g in grids.items()},
+          **({} if curve is None else {"dense_psnr_db_by_training_iterations": curve}))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=10)
@@ -413,8 +497,12 @@ def main():
     ap.add_argument("--march", action="store_true", help="time grid ray marching (DESIGN.md §16)")
     ap.add_argument("--mlp-precision", action="store_true", help="time the bf16 MLP forward (DESIGN.md §17)")
     ap.add_argument("--table-precision", action="store_true", help="time the fp16 hash tables (DESIGN.md §18)")
+    ap.add_argument("--march-stop", action="store_true", help="time stopping rays inside the march (DESIGN.md §19)")
+    ap.add_argument("--opaque-curve", default=None,
+                    help="--march-stop: training iteration counts to try in turn until the dense PSNR stops rising")
     a = ap.parse_args()
-    mode, out = ((main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
+    mode, out = ((main_march_stop, "profiles/march_stop_render_time.json") if a.march_stop else
+                 (main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
                  (main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
                  (main_march, "profiles/march_render_time.json") if a.march else
                  (main_early_stop, "profiles/early_stop_render_time.json") if a.early_stop else
