@@ -97,6 +97,29 @@ int nerf_hash_encode_fwd_half(const float* d_xyz, int64_t n_points,
                               float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
                               uint8_t* d_keep, void* stream);
 
+/* Forward-only rendering with packed bf16 features (additive, ABI 12). A packed feature buffer
+ * holds one uint32_t per (point, level): the low half is bf16_rne(f0) and the high half bf16_rne(f1) (round to
+ * nearest even), where f0, f1 are exactly the fp32 values the unpacked entry would have written. The word of
+ * (point p, level l) is d_featw[p * feat_stride_point + l * feat_stride_level]; the strides are in 4-byte words
+ * (level-major [L, P]: (1, P); point-major [P, L]: (L, 1)).
+ * nerf_hash_encode_fwd_pkbf is nerf_hash_encode_fwd with that output, nerf_hash_encode_fwd_half_pkbf is
+ * nerf_hash_encode_fwd_half with it: same checks, same grid, same voxel math, blend and keep rule, an empty batch
+ * accepts NULL per-point buffers. The words are what the bf16 MLP forward makes of the fp32 features before its
+ * first layer, so nerf_mlp_fwd_bf16_pkbf (below) on them gives nerf_mlp_fwd_bf16's raw on the unpacked features
+ * bit for bit. There is no backward for them. */
+int nerf_hash_encode_fwd_pkbf(const float* d_xyz, int64_t n_points,
+                              const float* bbox_min3, const float* bbox_max3,
+                              const float* level_res, int n_levels, int log2_T,
+                              const float* const* d_tables,
+                              uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                              uint8_t* d_keep, void* stream);
+int nerf_hash_encode_fwd_half_pkbf(const float* d_xyz, int64_t n_points,
+                                   const float* bbox_min3, const float* bbox_max3,
+                                   const float* level_res, int n_levels, int log2_T,
+                                   const void* d_half,
+                                   uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                   uint8_t* d_keep, void* stream);
+
 /* d_dtables: host array of n_levels device pointers; gradients are ACCUMULATED (atomic adds). */
 int nerf_hash_encode_bwd(const float* d_xyz, int64_t n_points,
                          const float* bbox_min3, const float* bbox_max3,
@@ -344,6 +367,16 @@ int nerf_mlp_fwd_bf16(const float* d_feat, int64_t feat_stride_point, int64_t fe
                       const uint8_t* d_keep, int64_t n_points,
                       const nerf_mlp_weights* weights, float* d_raw,
                       const nerf_point_order* order, void* stream);
+/* The same on packed bf16 features (additive, ABI 12): d_featw and its word strides as
+ * nerf_hash_encode_fwd_pkbf writes them, everything else nerf_mlp_fwd_bf16's (three SH modes, d_keep, order, tail
+ * lanes, fp32 sigma, exact fp32 C2). A lane loads the words and uses them as its matrix operand without a
+ * conversion; d_raw is, in every bit, nerf_mlp_fwd_bf16's on fp32 features that round to those words. */
+int nerf_mlp_fwd_bf16_pkbf(const uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                           const float* d_sh, int64_t sh_stride,
+                           const float* d_viewdirs, int64_t samples_per_ray,
+                           const uint8_t* d_keep, int64_t n_points,
+                           const nerf_mlp_weights* weights, float* d_raw,
+                           const nerf_point_order* order, void* stream);
 int nerf_mlp_bwd_q(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
                    const float* d_sh, int64_t sh_stride,
                    const float* d_viewdirs, int64_t samples_per_ray,

@@ -139,6 +139,10 @@ SIGNATURES = {
     "nerf_hash_tables_to_half": [ctypes.POINTER(c_vp), c_int, c_int, c_vp, c_vp],
     "nerf_hash_encode_fwd_half": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp,
                                   c_vp, c_i64, c_i64, c_vp, c_vp],
+    "nerf_hash_encode_fwd_pkbf": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, ctypes.POINTER(c_vp),
+                                  c_vp, c_i64, c_i64, c_vp, c_vp],
+    "nerf_hash_encode_fwd_half_pkbf": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp,
+                                       c_vp, c_i64, c_i64, c_vp, c_vp],
     "nerf_hash_encode_bwd": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp, c_i64, c_i64,
                              ctypes.POINTER(c_vp), c_vp],
     "nerf_hash_encode_bwd_ws": [c_vp, c_i64, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp, c_i64, c_i64,
@@ -170,6 +174,8 @@ SIGNATURES = {
                          c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(PointOrder), c_vp],
     "nerf_mlp_fwd_bf16": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
                           c_vp, ctypes.POINTER(PointOrder), c_vp],
+    "nerf_mlp_fwd_bf16_pkbf": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
+                               c_vp, ctypes.POINTER(PointOrder), c_vp],
     "nerf_mlp_fwd_h3": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
                         c_vp, c_vp, c_vp, c_vp, c_i64, ctypes.POINTER(PointOrder), c_vp, c_vp],
     "nerf_mlp_bwd_q": [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),

@@ -22,7 +22,7 @@ __global__ void __launch_bounds__(256) sh4_fwd_kernel(const float* __restrict__ 
 
 int launch_mlp_fwd_x6(const MlpArgs& a, hipStream_t stream);     // field_x6.hip
 int launch_mlp_act_minmax_x6(const MlpArgs& a, hipStream_t stream);
-int launch_mlp_fwd_bf16(const MlpArgs& a, hipStream_t stream);
+int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream);
 int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_t stream);
 
 static int fill_args(MlpArgs& a, const float* d_feat, int64_t sp, int64_t sl, const float* d_sh, int64_t sh_stride,
@@ -124,22 +124,41 @@ extern "C" int nerf_mlp_fwd(const float* d_feat, int64_t feat_stride_point, int6
                           d_keep, n_points, weights, d_raw, d_geo, nullptr, nullptr, 0, stream);
 }
 
-// The forward with one bf16 piece per operand (field_x6.hip mlp_fwd_bf16_kernel): forward-only rendering
-extern "C" int nerf_mlp_fwd_bf16(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
-                                 const float* d_sh, int64_t sh_stride, const float* d_viewdirs,
-                                 int64_t samples_per_ray, const uint8_t* d_keep, int64_t n_points,
-                                 const nerf_mlp_weights* weights, float* d_raw, const nerf_point_order* order,
-                                 void* stream) {
+// The forward with one bf16 piece per operand (field_x6.hip mlp_fwd_bf16_kernel): forward-only rendering.
+// packed (nerf_mlp_fwd_bf16_pkbf, mlp_fwd_bf16_kernel<true>): d_feat holds the packed bf16 words, strides in words.
+static int mlp_fwd_bf16(const char* who, bool packed, const float* d_feat, int64_t feat_stride_point,
+                        int64_t feat_stride_level, const float* d_sh, int64_t sh_stride, const float* d_viewdirs,
+                        int64_t samples_per_ray, const uint8_t* d_keep, int64_t n_points,
+                        const nerf_mlp_weights* weights, float* d_raw, const nerf_point_order* order, void* stream) {
     MlpArgs a{};
     int rc = fill_args(a, d_feat, feat_stride_point, feat_stride_level, d_sh, sh_stride, d_viewdirs, samples_per_ray,
                        d_keep, n_points, weights);
     if (rc) return rc;
     rc = fill_order(a, order);
     if (rc) return rc;
-    NERF_REQUIRE(n_points == 0 || d_raw, "mlp_fwd_bf16: null output");
+    NERF_REQUIRE(n_points == 0 || d_raw, "%s: null output", who);
     if (n_points == 0) return NERF_OK;
     a.raw = d_raw;
-    return launch_mlp_fwd_bf16(a, as_stream(stream));
+    return launch_mlp_fwd_bf16(a, packed, as_stream(stream));
+}
+
+extern "C" int nerf_mlp_fwd_bf16(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                                 const float* d_sh, int64_t sh_stride, const float* d_viewdirs,
+                                 int64_t samples_per_ray, const uint8_t* d_keep, int64_t n_points,
+                                 const nerf_mlp_weights* weights, float* d_raw, const nerf_point_order* order,
+                                 void* stream) {
+    return mlp_fwd_bf16("mlp_fwd_bf16", false, d_feat, feat_stride_point, feat_stride_level, d_sh, sh_stride,
+                        d_viewdirs, samples_per_ray, d_keep, n_points, weights, d_raw, order, stream);
+}
+
+extern "C" int nerf_mlp_fwd_bf16_pkbf(const uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                      const float* d_sh, int64_t sh_stride, const float* d_viewdirs,
+                                      int64_t samples_per_ray, const uint8_t* d_keep, int64_t n_points,
+                                      const nerf_mlp_weights* weights, float* d_raw, const nerf_point_order* order,
+                                      void* stream) {
+    return mlp_fwd_bf16("mlp_fwd_bf16_pkbf", true, reinterpret_cast<const float*>(d_featw), feat_stride_point,
+                        feat_stride_level, d_sh, sh_stride, d_viewdirs, samples_per_ray, d_keep, n_points, weights,
+                        d_raw, order, stream);
 }
 
 extern "C" int nerf_mlp_bwd_q(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,

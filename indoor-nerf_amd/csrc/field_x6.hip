@@ -31,7 +31,6 @@ namespace nerf {
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(3))) bf16x4 lds_bf16x4;
@@ -44,10 +43,7 @@ struct S3 {
 #define X6_MFMA(a, b, c) \
     __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, (a)), __builtin_bit_cast(bf16x8, (b)), (c), 0, 0, 0)
 
-__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
-    const bf16x2 v = {(__bf16)a, (__bf16)b};   // v_cvt_pk_bf16_f32: round to nearest even
-    return __builtin_bit_cast(uint32_t, v);
-}
+// pk_bf16 (v_cvt_pk_bf16_f32, round to nearest even): hash_common.h, shared with the packed-feature encoder
 
 __device__ __forceinline__ float lo_f(uint32_t p) { return __uint_as_float(p << 16); }
 __device__ __forceinline__ float hi_f(uint32_t p) { return __uint_as_float(p & 0xffff0000u); }
@@ -1447,10 +1443,33 @@ __device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, boo
     return pack_arr(shv);
 }
 
+// Packed bf16 features (mlp_fwd_bf16_kernel<true>, nerf_mlp_fwd_bf16_pkbf): a.feat holds one word
+// {bf16 f0, bf16 f1} per (point, level), written by the packed encoder (hashgrid_pkbf.hip) with pk_bf16, a.sp / a.sl
+// in words. Lane (j, h) loads the words of levels 8c + 4q + 2h + e and uses them as they are:
+// xb[c] = {W[8c+2h], W[8c+2h+1], W[8c+4+2h], W[8c+4+2h+1]} is what load_x6 (x[8c + 4q + 2e + i] = feature i of that
+// level) followed by pack_arr (dword d = pk(x[2d], x[2d+1])) produces from the fp32 features, so raw is the same
+// bits. Tail lanes read the last point's words (load_x6).
+__device__ __forceinline__ void load_x_pkbf(const MlpArgs& a, uint32_t pt, bool valid, int h, u32x4 (&xb)[2]) {
+    const uint32_t* __restrict__ fw = reinterpret_cast<const uint32_t*>(a.feat);
+    const uint32_t pc = valid ? pt : (uint32_t)(a.P - 1);
+#pragma unroll
+    for (int c = 0; c < 2; ++c)
+#pragma unroll
+        for (int q = 0; q < 2; ++q)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                const int level = 8 * c + 4 * q + 2 * h + e;
+                xb[c][2 * q + e] = fw[(uint32_t)(pc * (uint32_t)a.sp + level * (uint32_t)a.sl)];
+            }
+}
+
 // 512-thread blocks on the x6 forward's grid: at most two blocks per CU, 4 waves per SIMD. The chain needs 78
 // registers and no scratch, and the 22.3 KB image would allow more, but a tile's time is its ~425 VALU and
 // 20 MFMA issue slots, not latency: loading the next tile's inputs under the current chain (112 registers)
 // measured 37.7 us against 35.8 us per 786,432 points without it.
+// PK: the features are packed bf16 words (load_x_pkbf) and layer 0 takes them without a conversion; <false> is
+// the kernel as it was (the same instructions).
+template <bool PK>
 __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
     __shared__ __attribute__((aligned(16))) __bf16 img[IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
@@ -1464,7 +1483,9 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
         const uint32_t pt = (uint32_t)(tile * 32 + j);
         const bool valid = tile * 32 + j < a.P;
         float x[16];
-        load_x6(a, pt, valid, h, x, 0);
+        u32x4 xb[2];
+        if constexpr (PK) load_x_pkbf(a, pt, valid, h, xb);
+        else load_x6(a, pt, valid, h, x, 0);
         const u32x4 SH = load_sh_bf16(a, pt, valid, h);
         const int z = opaque_zero();
         const __bf16* im = img + z;
@@ -1472,7 +1493,10 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
         floatx16 h1[2];
         h1[0] = h1[1] = zero16();
         {
-            const u32x4 xb[2] = {pack_arr(x), pack_arr(x + 8)};
+            if constexpr (!PK) {
+                xb[0] = pack_arr(x);
+                xb[1] = pack_arr(x + 8);
+            }
 #pragma unroll
             for (int c = 0; c < 2; ++c)
 #pragma unroll
@@ -1523,14 +1547,17 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
     }
 }
 
-int launch_mlp_fwd_bf16(const MlpArgs& a, hipStream_t stream) {
-    NERF_REQUIRE(fits_u32(a), "mlp_fwd_bf16: %lld points exceed 32-bit indexing", (long long)a.P);
+// packed: a.feat holds packed bf16 words and a.sp / a.sl count words (the same 32-bit index bound: a word is 4 B)
+int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream) {
+    const char* who = packed ? "mlp_fwd_bf16_pkbf" : "mlp_fwd_bf16";
+    NERF_REQUIRE(fits_u32(a), "%s: %lld points exceed 32-bit indexing", who, (long long)a.P);
     NERF_REQUIRE(!a.aq && !a.act_minmax && !a.geo_out && !a.h3,
-                 "mlp_fwd_bf16: no A-CAQ record, geo output or saved h3 (forward-only rendering)");
+                 "%s: no A-CAQ record, geo output or saved h3 (forward-only rendering)", who);
     const int64_t tiles = (a.P + 31) / 32;
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
-    hipLaunchKernelGGL(mlp_fwd_bf16_kernel, dim3((unsigned)blocks), dim3(512), 0, stream, a);
-    NERF_CHECK_LAUNCH("mlp_fwd_bf16");
+    if (packed) hipLaunchKernelGGL(mlp_fwd_bf16_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    else hipLaunchKernelGGL(mlp_fwd_bf16_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    NERF_CHECK_LAUNCH(who);
     return NERF_OK;
 }
 

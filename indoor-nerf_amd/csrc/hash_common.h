@@ -1,6 +1,8 @@
 // Shared per-point voxel math of the hash-grid kernels (hashgrid.hip, quant.hip).
 #pragma once
 
+#include <hip/hip_fp16.h>
+
 #include "common.h"
 
 namespace nerf {
@@ -232,10 +234,10 @@ __device__ __forceinline__ void fwd_gather(float x, float y, float z, const Hash
     for (int c = 0; c < 4; ++c) s.e[c] = tab[spatial_hash3(bx, by + ((c >> 1) & 1), bz + (c & 1), hp.mask)];
 }
 
+// The blend of one (point, level): both lanes of the pair end with both features (ox_, oy_) of the point.
 template <bool QUANT>
-__device__ __forceinline__ void fwd_finish(FwdLvl& s, int lvl, int xb, bool valid, int64_t p,
-                                           float* __restrict__ feat, int64_t sp, int64_t sl,
-                                           uint8_t* __restrict__ keep, const QuantRec* __restrict__ qrec) {
+__device__ __forceinline__ void fwd_blend(FwdLvl& s, int lvl, int xb, const QuantRec* __restrict__ qrec, float& ox_,
+                                          float& oy_) {
     if constexpr (QUANT) {
         const QuantRec q = qrec[lvl];
 #pragma unroll
@@ -257,11 +259,79 @@ __device__ __forceinline__ void fwd_finish(FwdLvl& s, int lvl, int xb, bool vali
     // c00 = cx[0], c01 = cx[1], c10 = cx[2], c11 = cx[3]
     const float c0x = cx[0] * oy + cx[2] * wy, c1x = cx[1] * oy + cx[3] * wy;
     const float c0y = cy[0] * oy + cy[2] * wy, c1y = cy[1] * oy + cy[3] * wy;
-    const float ox_ = c0x * oz + c1x * wz, oy_ = c0y * oz + c1y * wz;
+    ox_ = c0x * oz + c1x * wz;
+    oy_ = c0y * oz + c1y * wz;
+}
+
+template <bool QUANT>
+__device__ __forceinline__ void fwd_finish(FwdLvl& s, int lvl, int xb, bool valid, int64_t p,
+                                           float* __restrict__ feat, int64_t sp, int64_t sl,
+                                           uint8_t* __restrict__ keep, const QuantRec* __restrict__ qrec) {
+    float ox_, oy_;
+    fwd_blend<QUANT>(s, lvl, xb, qrec, ox_, oy_);
     if (!valid) return;
     if (lvl == 0 && keep && xb == 0) keep[p] = s.inside ? 1 : 0;
     float* dst = feat + p * sp + (int64_t)lvl * sl;
     dst[xb] = xb ? oy_ : ox_;
+}
+
+// ---- the gather from the fp16 image (hashgrid_half.hip) -------------------------------
+// FwdLvl with the four corners as the image's raw words
+struct FwdLvlHalf {
+    float wx, wy, wz;
+    bool inside;
+    uint32_t e[4];   // corners (xb, j, k), index 2j + k: {f16 x, f16 y}
+};
+
+// fwd_gather with hp.tables[lvl] pointing at the level's 4-byte entries: one global_load_dword per corner
+template <bool FAST>
+__device__ __forceinline__ void fwd_gather_half(float x, float y, float z, const HashParams& hp, int lvl, int xb,
+                                                FwdLvlHalf& s) {
+    AxisCell ax, ay, az;
+    fwd_axes<FAST>(x, y, z, hp, lvl, xb, ax, ay, az);
+    s.wx = ax.w; s.wy = ay.w; s.wz = az.w;
+    s.inside = ax.inside && ay.inside && az.inside;
+    const uint32_t* __restrict__ tab = reinterpret_cast<const uint32_t*>(hp.tables[lvl]);
+    const uint32_t bx = (uint32_t)ax.base + (uint32_t)xb, by = (uint32_t)ay.base, bz = (uint32_t)az.base;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s.e[c] = tab[spatial_hash3(bx, by + ((c >> 1) & 1), bz + (c & 1), hp.mask)];
+}
+
+// binary16 -> fp32 is exact (v_cvt_f32_f16, fp16 subnormals included)
+__device__ __forceinline__ float2 half_entry_widen(uint32_t w) {
+    return make_float2(__half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu))),
+                       __half2float(__ushort_as_half((unsigned short)(w >> 16))));
+}
+
+// the level as fwd_finish / fwd_finish_pkbf take it
+__device__ __forceinline__ FwdLvl fwd_widen_half(const FwdLvlHalf& h) {
+    FwdLvl s;
+    s.wx = h.wx; s.wy = h.wy; s.wz = h.wz;
+    s.inside = h.inside;
+#pragma unroll
+    for (int c = 0; c < 4; ++c) s.e[c] = half_entry_widen(h.e[c]);
+    return s;
+}
+
+// ---- packed bf16 features (hashgrid_pkbf.hip, field_x6.hip mlp_fwd_bf16_kernel<true>) -----
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+
+// {bf16_rne(a), bf16_rne(b)}, a in the low half
+__device__ __forceinline__ uint32_t pk_bf16(float a, float b) {
+    const bf16x2 v = {(__bf16)a, (__bf16)b};   // v_cvt_pk_bf16_f32: round to nearest even
+    return __builtin_bit_cast(uint32_t, v);
+}
+
+// fwd_finish<false> with the point's two features of the level as one word {bf16 f0, bf16 f1}: after the blend
+// both lanes of the pair hold both values, so lane xb == 0 converts and stores and lane 1 stores nothing
+__device__ __forceinline__ void fwd_finish_pkbf(FwdLvl& s, int lvl, int xb, bool valid, int64_t p,
+                                                uint32_t* __restrict__ featw, int64_t sp, int64_t sl,
+                                                uint8_t* __restrict__ keep) {
+    float ox_, oy_;
+    fwd_blend<false>(s, lvl, xb, nullptr, ox_, oy_);
+    if (!valid || xb != 0) return;
+    if (lvl == 0 && keep) keep[p] = s.inside ? 1 : 0;
+    featw[p * sp + (int64_t)lvl * sl] = pk_bf16(ox_, oy_);
 }
 
 // ---- host side of the lane-pair forward, shared by nerf_hash_encode_fwd_q (hashgrid.hip) and

@@ -55,41 +55,12 @@ __global__ void __launch_bounds__(256) hash_tables_to_half_entry_kernel(HalfSrc 
 }
 
 // ---- the gather ---------------------------------------------------------------------------------------
-// FwdLvl (hash_common.h) with the four corners as the image's raw words
-struct FwdLvlHalf {
-    float wx, wy, wz;
-    bool inside;
-    uint32_t e[4];   // corners (xb, j, k), index 2j + k: {f16 x, f16 y}
-};
-
-// fwd_gather with hp.tables[lvl] pointing at the level's 4-byte entries: one global_load_dword per corner
-template <bool FAST>
-__device__ __forceinline__ void fwd_gather_half(float x, float y, float z, const HashParams& hp, int lvl, int xb,
-                                                FwdLvlHalf& s) {
-    AxisCell ax, ay, az;
-    fwd_axes<FAST>(x, y, z, hp, lvl, xb, ax, ay, az);
-    s.wx = ax.w; s.wy = ay.w; s.wz = az.w;
-    s.inside = ax.inside && ay.inside && az.inside;
-    const uint32_t* __restrict__ tab = reinterpret_cast<const uint32_t*>(hp.tables[lvl]);
-    const uint32_t bx = (uint32_t)ax.base + (uint32_t)xb, by = (uint32_t)ay.base, bz = (uint32_t)az.base;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s.e[c] = tab[spatial_hash3(bx, by + ((c >> 1) & 1), bz + (c & 1), hp.mask)];
-}
-
-// binary16 -> fp32 is exact (v_cvt_f32_f16, fp16 subnormals included)
-__device__ __forceinline__ float2 half_entry_widen(uint32_t w) {
-    return make_float2(__half2float(__ushort_as_half((unsigned short)(w & 0xFFFFu))),
-                       __half2float(__ushort_as_half((unsigned short)(w >> 16))));
-}
-
+// FwdLvlHalf, fwd_gather_half and the exact widening live in hash_common.h (the packed-feature kernel of
+// hashgrid_pkbf.hip gathers the same way)
 __device__ __forceinline__ void fwd_finish_half(const FwdLvlHalf& h, int lvl, int xb, bool valid, int64_t p,
                                                 float* __restrict__ feat, int64_t sp, int64_t sl,
                                                 uint8_t* __restrict__ keep) {
-    FwdLvl s;
-    s.wx = h.wx; s.wy = h.wy; s.wz = h.wz;
-    s.inside = h.inside;
-#pragma unroll
-    for (int c = 0; c < 4; ++c) s.e[c] = half_entry_widen(h.e[c]);
+    FwdLvl s = fwd_widen_half(h);
     fwd_finish<false>(s, lvl, xb, valid, p, feat, sp, sl, keep, nullptr);
 }
 

@@ -190,7 +190,10 @@ class FieldFn(torch.autograd.Function):
             raise NotImplementedError("run_network: gradients w.r.t. positions/directions are not implemented")
         n_tab = embedder.n_levels
         tables, weights, head = params[:n_tab], params[n_tab:n_tab + 5], params[n_tab + 5:]
-        bf16 = getattr(pts, "_nerf_mlp", None) is not None   # run_network's checked MlpRequest
+        mlp = getattr(pts, "_nerf_mlp", None)
+        bf16 = mlp is not None                               # run_network's checked MlpRequest
+        packed = bf16 and mlp.packed                         # its packed bf16 features
+        w = 1 if packed else 2                               # elements of feat per (point, level) entry
         half = getattr(pts, "_nerf_tab", None) is not None   # and its checked TableRequest
         pts = pts.contiguous()
         sh_rays = getattr(viewdirs, "_nerf_sh", None)   # render_rays' per-ray SH4 rows (sh_stride 0)
@@ -204,25 +207,27 @@ class FieldFn(torch.autograd.Function):
         ctx.reuse = order = None
         spr = samples_per_ray
         if (reuse is not None and plain and reuse.matches(embedder, tables, P)
+                and (reuse.feat.dtype == torch.int32) == packed
                 and (not net.use_quantization or n_calib >= P)):   # calibration over all points: any order
             # fine pass: the importance samples are gathered into the head rows of the reuse buffer, whose
             # tail holds the coarse pass's features; the MLP walks that importance-first order
             feat, keep, row0 = reuse.feat, reuse.keep, 0
-            embedder.encode_into(reuse.imp_pts.view(-1, 3), feat, 2, 2 * P, keep, half=half)
+            embedder.encode_into(reuse.imp_pts.view(-1, 3), feat, w, w * P, keep, half=half, packed=packed)
             order = (reuse.inv, reuse.R * reuse.N, reuse.S)
             spr = reuse.N
             reuse.state = "used"
             ctx.reuse = ("fine", reuse)
         elif reuse is not None and plain and reuse.state == "armed" and P == reuse.R * reuse.S:
-            feat, keep, row0 = reuse.alloc(n_tab, dev)      # coarse pass: the tail rows of the reuse buffer
-            embedder.encode_into(pts, feat, 2, 2 * feat.shape[1], keep, row0=row0, half=half)
+            feat, keep, row0 = reuse.alloc(n_tab, dev, packed)   # coarse pass: the tail rows of the reuse buffer
+            embedder.encode_into(pts, feat, w, w * feat.shape[1], keep, row0=row0, half=half, packed=packed)
             reuse.record(pts, embedder, tables)
             ctx.reuse = ("coarse", reuse)
         else:
-            feat = torch.empty(n_tab, P, 2, device=dev, dtype=torch.float32)
+            feat = (torch.empty(n_tab, P, device=dev, dtype=torch.int32) if packed
+                    else torch.empty(n_tab, P, 2, device=dev, dtype=torch.float32))
             keep, row0 = torch.empty(P, device=dev, dtype=torch.bool), 0
-            embedder.encode_into(pts, feat, 2, 2 * P, keep, half=half)
-        sl = 2 * feat.shape[1]
+            embedder.encode_into(pts, feat, w, w * P, keep, half=half, packed=packed)
+        sl = w * feat.shape[1]
         keep = keep[row0:row0 + P]                   # the MLP's keep flags, in its point order
         raw = torch.empty(P, 4, device=dev, dtype=torch.float32)
         o16 = torch.empty(P, 16, device=dev, dtype=torch.float32) if head else None
@@ -233,7 +238,7 @@ class FieldFn(torch.autograd.Function):
             view_args = (_lib.ptr(sh_rays, "sh_rows"), 0, None)
         else:
             view_args = (None, 0, _lib.ptr(viewdirs, "viewdirs"))
-        feat_args = (_lib.ptr_at(feat, 2 * row0, "feat"), 2, sl, *view_args, spr, keep_arg)
+        feat_args = (_lib.ptr_at(feat, w * row0, "feat", feat.dtype), w, sl, *view_args, spr, keep_arg)
         w0q, arec = net.quant_state(lambda w0q: _act_calibration(feat_args, P, weights, w0q, n_calib))
         # a training forward keeps layer C1's outputs for the backward (nerf_mlp_fwd_h3: 256 B per point;
         # the backward then skips C1's recompute) — not with the activation quantizer (its backward
@@ -243,8 +248,8 @@ class FieldFn(torch.autograd.Function):
                 and any(ctx.needs_input_grad[7:7 + n_tab + 5])):
             h3 = torch.empty(int(_lib.load().nerf_mlp_h3_bytes(P)) // 4, device=dev, dtype=torch.float32)
         if bf16:   # forward-only: no head, no quantizers, no gradients (sparse_field.check_mlp_field)
-            _lib.call("nerf_mlp_fwd_bf16", *feat_args, P, _weights_struct(weights), _lib.ptr(raw, "raw"),
-                      _point_order(order), _lib.stream())
+            _lib.call("nerf_mlp_fwd_bf16_pkbf" if packed else "nerf_mlp_fwd_bf16", *feat_args, P,
+                      _weights_struct(weights), _lib.ptr(raw, "raw"), _point_order(order), _lib.stream())
         else:
             _lib.call("nerf_mlp_fwd_h3", *feat_args, P, _weights_struct(weights, w0q), _lib.ptr(raw, "raw"),
                       _lib.ptr(o16, "geo", allow_none=True), _lib.ptr(arec, "act_record", allow_none=True), None, 0,

@@ -540,6 +540,7 @@ def hash_encode_bwd(xyz, meta, dfeat, sp, sl, grad_tables, defer=None, queue=Tru
 
 
 HALF_ACAQ = "encode_into: half tables are not available with A-CAQ quantizers (they have their own packed tables)"
+PACKED_ACAQ = "encode_into: packed bf16 features are not available with A-CAQ quantizers (the bf16 MLP has no record)"
 
 
 class HashEmbedder(nn.Module):
@@ -662,23 +663,34 @@ class HashEmbedder(nn.Module):
             st["key"] = key
         return st["buf"]
 
-    def encode_into(self, xyz, feat, sp, sl, keep, row0=0, half=False):
+    def encode_into(self, xyz, feat, sp, sl, keep, row0=0, half=False, packed=False):
         """Forward gather into caller-allocated feat/keep on the path this forward needs: plain,
         fake-quantized (training / STE) or int-packed (eval-mode quantizers). row0: the points land in
         rows row0 .. row0 + n of feat (level-major, point stride sp, level stride sl) and keep.
-        half (forward-only rendering): gather from half_tables() instead of the fp32 tables."""
+        half (forward-only rendering): gather from half_tables() instead of the fp32 tables.
+        packed (forward-only rendering): feat is an int32 buffer of packed bf16 words, one
+        {bf16 f0, bf16 f1} per (point, level), and sp, sl count words (nerf_hash_encode_fwd_pkbf, with half
+        nerf_hash_encode_fwd_half_pkbf)."""
         if half and self.quantization_active():
             raise ValueError(HALF_ACAQ)
+        if packed and self.quantization_active():
+            raise ValueError(PACKED_ACAQ)
         meta = self._meta
         P = xyz.shape[0]
-        if P > 0 and ((row0 + P - 1) * sp + (self.n_levels - 1) * sl + 2 > feat.numel() or row0 + P > keep.numel()):
+        w, fdt = (1, torch.int32) if packed else (2, torch.float32)   # elements per (point, level) entry
+        if P > 0 and ((row0 + P - 1) * sp + (self.n_levels - 1) * sl + w > feat.numel() or row0 + P > keep.numel()):
             raise ValueError("encode_into: rows out of the feature / keep buffers")
-        fp = _lib.ptr_at(feat, sp * row0, "feat")
+        fp = _lib.ptr_at(feat, sp * row0, "feat", dtype=fdt)
         kp = _lib.ptr_at(keep, row0, "keep", dtype=torch.bool)
         if half:
-            _lib.call("nerf_hash_encode_fwd_half", _lib.ptr(xyz, "xyz"), P, meta["bmin"], meta["bmax"], meta["res"],
-                      self.n_levels, meta["log2_T"], _lib.ptr(self.half_tables(), "half_tables", dtype=torch.uint8),
-                      fp, sp, sl, kp, _lib.stream())
+            _lib.call("nerf_hash_encode_fwd_half_pkbf" if packed else "nerf_hash_encode_fwd_half", _lib.ptr(xyz, "xyz"),
+                      P, meta["bmin"], meta["bmax"], meta["res"], self.n_levels, meta["log2_T"],
+                      _lib.ptr(self.half_tables(), "half_tables", dtype=torch.uint8), fp, sp, sl, kp, _lib.stream())
+            return
+        if packed:   # forward-only: every pending table gate is joined first, as for the fp16 image
+            join_tables(xyz.device)
+            _lib.call("nerf_hash_encode_fwd_pkbf", _lib.ptr(xyz, "xyz"), P, meta["bmin"], meta["bmax"], meta["res"],
+                      self.n_levels, meta["log2_T"], _lib.ptr_array(self.tables()), fp, sp, sl, kp, _lib.stream())
             return
         key, L = str(xyz.device), self.n_levels
         plain = not self.quantization_active()

@@ -330,10 +330,12 @@ class CoarseReuse:
         self.feat = self.keep = self.pts = self.embedder = self.versions = None
         self.inv = self.imp_pts = None
 
-    def alloc(self, n_levels, device):
-        """The shared feature / keep buffers; returns them and the coarse pass's first row."""
+    def alloc(self, n_levels, device, packed=False):
+        """The shared feature / keep buffers; returns them and the coarse pass's first row. packed: the features as
+        bf16 words [L, P] int32 (feature_precision="bf16")."""
         P = self.R * (self.S + self.N)
-        self.feat = torch.empty(n_levels, P, 2, device=device, dtype=torch.float32)
+        self.feat = (torch.empty(n_levels, P, device=device, dtype=torch.int32) if packed
+                     else torch.empty(n_levels, P, 2, device=device, dtype=torch.float32))
         self.keep = torch.empty(P, device=device, dtype=torch.bool)
         return self.feat, self.keep, self.R * self.N
 
@@ -389,13 +391,14 @@ def _query_tab(network_query_fn, pts, viewdirs, fn, half):
     return raw
 
 
-def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half=False):
-    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16"); half:
-    with a TableRequest beside it (_query_tab)."""
+def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half=False, packed=False):
+    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16"), packed:
+    one that asks for packed bf16 features (feature_precision="bf16"); half: with a TableRequest beside it
+    (_query_tab)."""
     if not bf16:
         return _query_tab(network_query_fn, pts, viewdirs, fn, half)
     from .sparse_field import MlpRequest
-    req = pts._nerf_mlp = MlpRequest()
+    req = pts._nerf_mlp = MlpRequest(packed=packed)
     try:
         raw = _query_tab(network_query_fn, pts, viewdirs, fn, half)
     finally:
@@ -405,14 +408,14 @@ def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half=False):
     return raw
 
 
-def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False, half=False):
+def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False, half=False, packed=False):
     """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
     (stops int32 [R], early_stop.py), None otherwise (stops None)."""
     if occupancy is None and early is None:
-        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half), None
+        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half, packed), None
     from .sparse_field import SparseRequest
     req = pts._nerf_sparse = SparseRequest(occupancy, early)
-    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half)
+    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half, packed)
     del pts._nerf_sparse
     if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
         raise ValueError(f"render_rays: {req.what} needs a network_query_fn that calls this package's run_network")
@@ -430,7 +433,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
-                table_precision=None, march_stop=None, march_stop_slab=128):
+                table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -464,7 +467,13 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     did); march_samples then counts the samples actually evaluated. Each map differs from the unstopped march's by
     at most eps. With retraw the packed entries come per slab: march_slabs, a list of (offsets, raw, pts, z_vals).
     Composes with mlp_precision=, table_precision= and render's ray_bounds=. None (the default) is the march
-    without it: no other launch, no other buffer."""
+    without it: no other launch, no other buffer.
+    feature_precision (None, "fp32" or "bf16"; with mlp_precision="bf16"): "bf16" makes every
+    hash-encoding launch of the call write one word {bf16 f0, bf16 f1} per (point, level) instead of two floats
+    (nerf_hash_encode_fwd_pkbf, with fp16 tables nerf_hash_encode_fwd_half_pkbf) and every MLP forward launch read
+    those words (nerf_mlp_fwd_bf16_pkbf): the rounding the bf16 MLP does first, done by the encoder, so the result is
+    bit for bit the mlp_precision="bf16" render at half the feature bytes. Composes with occupancy=, early_stop=,
+    march=, march_stop=, table_precision= and render's ray_bounds=. None and "fp32" are the call without it."""
     half = False
     if table_precision is not None:
         from .sparse_field import check_table_nets, check_table_precision
@@ -477,6 +486,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         bf16 = check_mlp_precision(mlp_precision, "render_rays")
     if bf16:
         check_mlp_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn, predict_normals)
+    packed = False
+    if feature_precision is not None:
+        from .sparse_field import check_feature_precision
+        packed = check_feature_precision(feature_precision, bf16, "render_rays")
     if march_stop is not None and march is None:
         from .sparse_field import check_march_stop
         check_march_stop(march_stop, march_stop_slab, march, "render_rays")
@@ -485,7 +498,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  bf16=bf16, half=half, march_stop=march_stop, march_stop_slab=march_stop_slab)
+                                  bf16=bf16, half=half, march_stop=march_stop, march_stop_slab=march_stop_slab,
+                                  packed=packed)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -524,7 +538,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
     raw, stops = _query(network_query_fn, pts, viewdirs, network_fn, occupancy,
-                        None if early is None else (z, rays_d) + early, bf16, half)
+                        None if early is None else (z, rays_d) + early, bf16, half, packed)
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -566,7 +580,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
             pts._nerf_reuse = reuse
         stops0 = stops
         raw, stops = _query(network_query_fn, pts, viewdirs, run_fn, occupancy,
-                            None if early is None else (z, rays_d) + early, bf16, half)
+                            None if early is None else (z, rays_d) + early, bf16, half, packed)
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()
@@ -629,7 +643,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
                        predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False,
-                       march_stop=None, march_stop_slab=128):
+                       march_stop=None, march_stop_slab=128, packed=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing. With march_stop the same in slabs
     (_march_slabs)."""
@@ -643,7 +657,7 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
         """The field on a packed list of n > 0 points."""
         from .sparse_field import MarchRequest
         req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
-        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half)
+        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half, packed)
         del pts_c._nerf_sparse
         if not req.used:   # a foreign query function ignores the attribute: never fall back silently
             raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
@@ -892,8 +906,8 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     default) leaves the call as it is without it.
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
     spans its own [near', far']. mlp_precision and table_precision go to
-    render_rays as well, and so do march_stop and march_stop_slab. retraw is refused with march: the
-    packed entries of several chunks do not concatenate."""
+    render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
+    §20). retraw is refused with march: the packed entries of several chunks do not concatenate."""
     if kwargs.get("march_stop") is not None:   # also when no chunk reaches render_rays
         from .sparse_field import check_march_stop
         check_march_stop(kwargs["march_stop"], kwargs.get("march_stop_slab", 128), kwargs.get("march"), "render")
@@ -902,9 +916,13 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
                          "concatenate; call render_rays on one chunk)")
     if ray_bounds is not None:
         _check_ray_bounds(ray_bounds)
+    bf16 = False
     if kwargs.get("mlp_precision") is not None:   # also when no chunk reaches render_rays (ray_bounds with every ray missed)
         from .sparse_field import check_mlp_precision
-        check_mlp_precision(kwargs["mlp_precision"], "render")
+        bf16 = check_mlp_precision(kwargs["mlp_precision"], "render")
+    if kwargs.get("feature_precision") is not None:   # likewise
+        from .sparse_field import check_feature_precision
+        check_feature_precision(kwargs["feature_precision"], bf16, "render")
     if kwargs.get("table_precision") is not None:   # likewise
         from .sparse_field import check_table_nets, check_table_precision
         if check_table_precision(kwargs["table_precision"], "render"):

@@ -19,7 +19,8 @@ from .occupancy import _check_modules
 NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop": "rays are not stopped in training",
                    "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training",
                    "mlp_precision": "the backward recomputes the forward in fp32",
-                   "table_precision": "the backward scatters into the fp32 tables"}
+                   "table_precision": "the backward scatters into the fp32 tables",
+                   "feature_precision": "the backward reads fp32 features"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -54,11 +55,13 @@ class MlpRequest:
     """render_rays' request of the bf16 MLP forward (mlp_precision="bf16"), attached to the point
     tensor of every pass as `pts._nerf_mlp`, beside a SparseRequest / MarchRequest when there is one. run_network
     sets `used` (a foreign query function leaves it False and render_rays raises) and routes every MLP forward
-    launch of the call to nerf_mlp_fwd_bf16."""
+    launch of the call to nerf_mlp_fwd_bf16. packed (feature_precision="bf16"): the feature buffers
+    of the call hold one word {bf16 f0, bf16 f1} per (point, level); every hash-encoding launch then goes to the
+    _pkbf entry of its tables and every MLP forward launch to nerf_mlp_fwd_bf16_pkbf."""
     what = "mlp_precision"
 
-    def __init__(self):
-        self.used = False
+    def __init__(self, packed=False):
+        self.used, self.packed = False, bool(packed)
 
 
 def check_mlp_precision(value, prefix):
@@ -95,11 +98,42 @@ def check_mlp_field(call_ok, shape_words, fn, embed_fn):
         raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
 
 
+def check_feature_precision(value, mlp_bf16, prefix):
+    """feature_precision of `prefix` (render_rays, render) -> whether it asks for packed bf16 features; its refusals:
+    an unknown value, a call whose MLP is not the bf16 one (mlp_bf16: check_mlp_precision's answer), gradients
+    enabled."""
+    if value is None or (isinstance(value, str) and value == "fp32"):
+        return False
+    if not (isinstance(value, str) and value == "bf16"):
+        raise ValueError(f"{prefix}: feature_precision must be None, 'fp32' or 'bf16', got {value!r}")
+    if not mlp_bf16:
+        raise ValueError(f"{prefix}: feature_precision='bf16' needs mlp_precision='bf16' (the fp32-accurate MLP reads "
+                         "fp32 features)")
+    check_forward_only("feature_precision", prefix)
+    return True
+
+
+def is_packed(mlp):
+    """Whether the field call of MlpRequest `mlp` (or None) keeps packed bf16 features."""
+    return mlp is not None and mlp.packed
+
+
+def feature_buffer(mlp, n, device):
+    """An uninitialised flat feature buffer of n (point, level) entries for the field call of MlpRequest `mlp` (or
+    None) -> (buffer, w, dtype): w elements per entry, 2 float32 or, packed, 1 int32 word (half the bytes)."""
+    if is_packed(mlp):
+        return torch.empty(n, device=device, dtype=torch.int32), 1, torch.int32
+    return torch.empty(2 * n, device=device, dtype=torch.float32), 2, torch.float32
+
+
 def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order):
-    """The MLP launch of the sparse field calls: n points with level-major features (level stride sl) and SH rows
-    at stride 16 -> their rows of raw (order: a nerf_point_order or None); mlp: the call's MlpRequest or None."""
-    front = (feat, 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
-    if mlp is not None:
+    """The MLP launch of the sparse field calls: n points with level-major features (level stride sl; packed: in
+    words, point stride 1) and SH rows at stride 16 -> their rows of raw (order: a nerf_point_order or None); mlp:
+    the call's MlpRequest or None."""
+    front = (feat, 1 if is_packed(mlp) else 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
+    if is_packed(mlp):
+        _lib.call("nerf_mlp_fwd_bf16_pkbf", *front, order, _lib.stream())
+    elif mlp is not None:
         _lib.call("nerf_mlp_fwd_bf16", *front, order, _lib.stream())
     else:
         _lib.call("nerf_mlp_fwd_ord", *front, None, None, None, 0, order, _lib.stream())
@@ -225,11 +259,12 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     pts = inputs.detach().float().contiguous()
     weights = _weights_struct(fn.mlp_weights())
     m = min(n, req.max_points)
-    feat, keep = torch.empty(L * m * 2, **f), torch.empty(m, device=dev, dtype=torch.bool)
+    (feat, w, fdt), keep = feature_buffer(mlp, L * m, dev), torch.empty(m, device=dev, dtype=torch.bool)
     for s0 in range(0, n, m):
         k = min(m, n - s0)
-        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * 2], 2, 2 * k, keep[:k], half=tab is not None)
-        mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
+        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * w], w, w * k, keep[:k], half=tab is not None,
+                             packed=is_packed(mlp))
+        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
                     _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None)
     return raw
 
@@ -261,18 +296,20 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     raw = torch.empty(P, 4, **f)
     weights = _weights_struct(fn.mlp_weights())
 
+    _, w, fdt = feature_buffer(mlp, 0, dev)   # elements per (point, level) entry of the call's feature buffers
+
     def field(n, rows, pts_c, sh_c, feat, keep):
         """The field at the n compacted points; rows of raw `rows` receive the results."""
-        embed_fn.encode_into(pts_c, feat, 2, 2 * n, keep, half=tab is not None)
-        mlp_forward(mlp, _lib.ptr(feat, "feat"), 2 * n, _lib.ptr(sh_c, "sh_c"), _lib.ptr(keep, "keep", torch.bool), n,
-                    weights, _lib.ptr(raw, "raw"), _point_order((rows, 0, 0)))
+        embed_fn.encode_into(pts_c, feat, w, w * n, keep, half=tab is not None, packed=is_packed(mlp))
+        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * n, _lib.ptr(sh_c, "sh_c"),
+                    _lib.ptr(keep, "keep", torch.bool), n, weights, _lib.ptr(raw, "raw"), _point_order((rows, 0, 0)))
 
     if req.early is None:
         # one slab, no alive flags: the grid's own compaction, every buffer sized exactly after the count
         rows, pts_c, sh_c = req.grid.compact(pts, viewdirs, S, raw)
         n = rows.shape[0]
         if n > 0:
-            field(n, rows, pts_c, sh_c, torch.empty(L, n, 2, **f), torch.empty(n, device=dev, dtype=torch.bool))
+            field(n, rows, pts_c, sh_c, feature_buffer(mlp, L * n, dev)[0], torch.empty(n, device=dev, dtype=torch.bool))
         return raw.reshape(R, S, 4)
 
     z, rays_d = z.detach().float().contiguous(), rays_d.detach().float().contiguous()
@@ -290,7 +327,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     count = torch.empty(1, **i32)
     ws = torch.empty(int(_lib.load().nerf_ert_compact_workspace_bytes(cap)) // 4, **i32)
     rows, pts_c, sh_c = torch.empty(cap, **i32), torch.empty(cap, 3, **f), torch.empty(cap, 16, **f)
-    feat, keep = torch.empty(L * cap * 2, **f), torch.empty(cap, device=dev, dtype=torch.bool)
+    feat, keep = feature_buffer(mlp, L * cap, dev)[0], torch.empty(cap, device=dev, dtype=torch.bool)
     evaluated = 0
 
     def compact(s0, s1, stages, n):
@@ -307,7 +344,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
         n = int(count.item())      # one 4-byte host read per slab sizes the encode and MLP launches
         compact(s0, s1, 2, n)
         if n > 0:
-            field(n, rows, pts_c[:n], sh_c, feat[:L * n * 2], keep[:n])
+            field(n, rows, pts_c[:n], sh_c, feat[:L * n * w], keep[:n])
         evaluated += n
         if s1 < S:
             _lib.call("nerf_ert_advance", _lib.ptr(raw, "raw"), _lib.ptr(z, "z"), _lib.ptr(rays_d, "rays_d"), R, S,

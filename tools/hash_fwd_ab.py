@@ -8,6 +8,9 @@ ratio of the medians, and whether the fp16 launch gives the fp32 launch's bits o
 
 --variant NAME=LIB (repeatable): the fp16 launch of another build of the library (tools/build_variant.py) joins the
 alternation in the same process, as "fp16:NAME".
+--feature-precision: the packed bf16 launches of both table formats (nerf_hash_encode_fwd_pkbf,
+nerf_hash_encode_fwd_half_pkbf) join the alternation as "fp32:pkbf" and "fp16:pkbf": the ratio of each
+unpacked launch's median to its packed twin's, and whether the words are the rounded features.
 --counter-run: a few launches of each and nothing else, to run under the profiler's counter collection on its own
 (no tracing beside it):  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d DIR -o t -- \\
     python tools/hash_fwd_ab.py --counter-run
@@ -26,7 +29,8 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
 
 SHAPES = ((4096, 64), (4096, 192), (32768, 192))
-KERNELS = ("hash_encode_fwd_pair_kernel", "hash_encode_fwd_half_pair_kernel", "hash_tables_to_half_kernel")
+KERNELS = ("hash_encode_fwd_pair_kernel", "hash_encode_fwd_half_pair_kernel", "hash_tables_to_half_kernel",
+           "hash_encode_fwd_pkbf_kernel<false>", "hash_encode_fwd_pkbf_kernel<true>")
 
 
 def counters(path):
@@ -53,6 +57,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--per-round", type=int, default=20)
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB")
+    ap.add_argument("--feature-precision", action="store_true")
     ap.add_argument("--counter-run", action="store_true")
     ap.add_argument("--counters", default=None)
     ap.add_argument("--out", default=None)
@@ -106,6 +111,15 @@ def run(a):
         feat = {k: torch.empty(L, P, 2, device=dev) for k in ["fp32", "fp16", "twin"] + ["fp16:" + v for v in variants]}
         keep = {k: torch.empty(P, device=dev, dtype=torch.bool) for k in feat}
 
+        packed = ["fp32:pkbf", "fp16:pkbf"] if a.feature_precision else []
+        words = {k: torch.empty(L, P, device=dev, dtype=torch.int32) for k in packed}
+        keep.update({k: torch.empty(P, device=dev, dtype=torch.bool) for k in packed})
+
+        def launch_pk(kind, name, tables):
+            _lib.call(name, _lib.ptr(pts), P, meta["bmin"], meta["bmax"], meta["res"], L, meta["log2_T"], tables,
+                      _lib.ptr(words[kind], dtype=torch.int32), 1, P, _lib.ptr(keep[kind], dtype=torch.bool),
+                      _lib.stream())
+
         def launch(kind, name, tables):
             _lib.call(name, _lib.ptr(pts), P, meta["bmin"], meta["bmax"], meta["res"], L, meta["log2_T"], tables,
                       _lib.ptr(feat[kind]), 2, 2 * P, _lib.ptr(keep[kind], dtype=torch.bool), _lib.stream())
@@ -121,6 +135,10 @@ def run(a):
 
         for vname in variants:
             fns["fp16:" + vname] = (lambda v=vname: variant_launch(v))
+        if packed:
+            fns["fp32:pkbf"] = lambda: launch_pk("fp32:pkbf", "nerf_hash_encode_fwd_pkbf", tabs)
+            fns["fp16:pkbf"] = lambda: launch_pk("fp16:pkbf", "nerf_hash_encode_fwd_half_pkbf",
+                                                 _lib.ptr(image, dtype=torch.uint8))
         if a.counter_run:
             for _ in range(4):
                 for fn in fns.values():
@@ -149,6 +167,12 @@ def run(a):
             row[f"fp16_over_fp16:{vname}"] = round(float(np.median(ts["fp16"]) / np.median(ts["fp16:" + vname])), 3)
             row[f"fp16:{vname}_same_bits"] = bool(torch.equal(feat["fp16:" + vname].view(torch.int32),
                                                               feat["fp16"].view(torch.int32)))
+        for kind in packed:
+            base = kind.split(":")[0]
+            row[f"{base}_over_{kind}"] = round(float(np.median(ts[base]) / np.median(ts[kind])), 3)
+            ref = feat[base].to(torch.bfloat16).contiguous().view(torch.int32).reshape(L, P)
+            row[f"{kind}_words_are_the_rounded_features"] = bool(torch.equal(words[kind], ref)
+                                                                 and torch.equal(keep[kind], keep[base]))
         row["inside_box"] = round(float(keep["fp16"].float().mean()), 4)
         row["fp16_equals_fp32_on_rounded_tables"] = bool(
             torch.equal(feat["fp16"].view(torch.int32), feat["twin"].view(torch.int32))

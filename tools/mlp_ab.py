@@ -5,7 +5,16 @@ checksum of every output (dfeat of both nets, the ten weight gradients) so that 
 compute the same thing; and of the MLP forward at the step's two point counts (262,144 and 786,432), the
 fp32-accurate kernel (nerf_mlp_fwd) and the bf16 one (nerf_mlp_fwd_bf16) alternating, where the
 library has it. A/B of library builds: run once per build with NERF_HIP_LIB=<path>
-(tools/build_variant.py). JSON out."""
+(tools/build_variant.py). JSON out.
+
+--feature-precision: only the A/B of the bf16 forward on fp32 features (nerf_mlp_fwd_bf16) against the same forward on
+packed bf16 words (nerf_mlp_fwd_bf16_pkbf), real features of the lego hash configuration: at 262,144
+points with the features hot (written once, the two launches alternate) and at 6,291,456 points with them not
+resident in cache (each timed launch follows an encode launch of that size into its buffer: 805 MB of fp32
+features, 403 MB of words). Median and min in us per launch, the ratio of the medians, whether raw has the same bits.
+--counter-run (with --feature-precision): a few launch pairs and nothing else, to run under the profiler's counter
+collection on its own. --out FILE also writes the JSON."""
+import argparse
 import ctypes
 import json
 import os
@@ -81,8 +90,91 @@ def forward_ab(jobs, dev, rounds=5, per_round=20):
     return out
 
 
+def packed_ab(dev, counter_run=False, rounds=5, per_round=20):
+    """The --feature-precision table: see the module docstring."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from tables import blender_bbox
+    lo, hi = blender_bbox()
+    emb = nerf.HashEmbedder((torch.from_numpy(lo), torch.from_numpy(hi)), finest_resolution=1024).to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(0)
+    net = nerf.NeRFSmall(2, 64, 15, 3, 64, 32, 16).to(dev)
+    w = _lib.MlpWeights(*[_lib.ptr(p.detach()).value for p in net.mlp_weights()])
+    with torch.no_grad():
+        for e in emb.embeddings:
+            e.weight.copy_((torch.rand(e.weight.shape, device=dev, generator=g) * 2 - 1) * 0.05)
+    L = emb.n_levels
+    out = {}
+    for R, S, cold in ((4096, 64, False), (32768, 192, True)):
+        P = R * S
+        o = 4.0 * torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        d = torch.nn.functional.normalize(-o + 0.8 * torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        t = torch.linspace(2.0, 6.0, S, device=dev)
+        pts = (o[:, None] + d[:, None] * t[None, :, None]).reshape(-1, 3).contiguous()
+        feat, words = torch.empty(L, P, 2, device=dev), torch.empty(L, P, device=dev, dtype=torch.int32)
+        keep = torch.empty(P, device=dev, dtype=torch.bool)
+        raws = {"bf16": torch.empty(P, 4, device=dev), "bf16:pkbf": torch.empty(P, 4, device=dev)}
+        back = (None, 0, _lib.ptr(d), S, _lib.ptr(keep, dtype=torch.bool), P, ctypes.byref(w))
+        with torch.no_grad():
+            enc = {"bf16": lambda: emb.encode_into(pts, feat, 2, 2 * P, keep),
+                   "bf16:pkbf": lambda: emb.encode_into(pts, words, 1, P, keep, packed=True)}
+        fns = {"bf16": lambda: _lib.call("nerf_mlp_fwd_bf16", _lib.ptr(feat), 2, 2 * P, *back, _lib.ptr(raws["bf16"]),
+                                         None, _lib.stream()),
+               "bf16:pkbf": lambda: _lib.call("nerf_mlp_fwd_bf16_pkbf", _lib.ptr(words, dtype=torch.int32), 1, P, *back,
+                                              _lib.ptr(raws["bf16:pkbf"]), None, _lib.stream())}
+        with torch.no_grad():
+            for name in fns:
+                enc[name]()
+                fns[name]()
+            torch.cuda.synchronize()
+            if counter_run:
+                for _ in range(3):
+                    for name in fns:
+                        if cold:
+                            enc[name]()
+                        fns[name]()
+                torch.cuda.synchronize()
+                continue
+            ts = {name: [] for name in fns}
+            for _ in range(rounds):
+                for fn in fns.values():
+                    for _ in range(3):
+                        fn()
+                torch.cuda.synchronize()
+                for _ in range(per_round if not cold else max(4, per_round // 2)):
+                    for name, fn in fns.items():
+                        if cold:      # the features written by a preceding encode of this size, as in a frame
+                            enc[name]()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        fn()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ts[name].append(e0.elapsed_time(e1))
+        row = {name + "_us_median": round(float(np.median(v)) * 1e3, 1) for name, v in ts.items()}
+        row.update({name + "_us_min": round(float(np.min(v)) * 1e3, 1) for name, v in ts.items()})
+        row["bf16_over_bf16:pkbf"] = round(float(np.median(ts["bf16"]) / np.median(ts["bf16:pkbf"])), 3)
+        row["features"] = "written by a preceding encode launch" if cold else "hot"
+        row["feature_bytes"] = {"bf16": feat.numel() * 4, "bf16:pkbf": words.numel() * 4}
+        row["raw_same_bits"] = bool(torch.equal(raws["bf16"].view(torch.int32), raws["bf16:pkbf"].view(torch.int32)))
+        out[str(P)] = row
+    return out
+
+
 def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--feature-precision", action="store_true")
+    ap.add_argument("--counter-run", action="store_true")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
     dev = torch.device("cuda:0")
+    if a.feature_precision:
+        report = {"device": torch.cuda.get_device_name(0), "packed_ab": packed_ab(dev, a.counter_run)}
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, "w") as fp:
+                json.dump(report, fp, indent=1)
+        print(json.dumps(report))
+        return
     torch.manual_seed(0)
     jf, kf = make_job(4096 * 192, 192, 1, dev)
     jc, kc = make_job(4096 * 64, 64, 2, dev)

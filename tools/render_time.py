@@ -54,6 +54,13 @@ frame with a pair of device events around each. --iters sets the training iterat
 tables); --opaque-curve 300,1000,... trains the scene afresh at each count in turn, records the dense PSNR and runs the
 table at the first count after which the dense PSNR rises by less than 0.1 dB (the last count if none).
 
+With --feature-precision the same frame, process and method time packed bf16 features instead
+(render(mlp_precision="bf16", feature_precision="bf16"), csrc/hashgrid_pkbf.hip): the dense frame and
+march= at 192 lattice samples through the geometry grid and the default grid, each with mlp_precision="bf16" without
+and with the keyword, on fp32 and on fp16 tables. Per variant: the frame time and its ratio to the unpacked twin's,
+whether the image has the twin's bits, and from one extra frame with a pair of device events around every launch the
+sums of the hash-encoding and of the MLP forward launches.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
@@ -413,6 +420,41 @@ def main_table_precision(a):
                                                 "default grid": default.occupied_fraction()})
 
 
+def main_feature_precision(a):
+    """The packed bf16 feature table: every row renders with mlp_precision="bf16", without and with
+    feature_precision="bf16", on fp32 and on fp16 tables; the pair must give the same image bit for bit."""
+    s = setup(a)
+    geo, default = s.new_grid("geometry"), s.new_grid("default")
+    rows = [("dense", {}), ("geometry grid: march, K = 192", dict(march=geo, march_samples=192)),
+            ("default grid: march, K = 192", dict(march=default, march_samples=192))]
+    variants, twin = [("dense", {})], {}      # the fp32 dense frame: measure()'s reference for speedup_vs_dense
+    for tab in ("fp32", "fp16"):
+        for name, over in rows:
+            base = name + ", bf16 MLP" + ("" if tab == "fp32" else ", fp16 tables")
+            over = dict(over, mlp_precision="bf16", **({} if tab == "fp32" else dict(table_precision="fp16")))
+            variants += [(base, over), (base + ", bf16 features", dict(over, feature_precision="bf16"))]
+            twin[base + ", bf16 features"] = base
+
+    report, images = {}, {}
+    for name, over in variants:         # untimed frames: PSNR, and where the launches' time goes
+        images[name] = s.frame(over)[0]
+        ms = launch_times(s, over)
+        enc = sum(v for k, v in ms.items() if k.startswith("nerf_hash_encode_fwd"))
+        mlp = sum(v for k, v in ms.items() if k.startswith("nerf_mlp_fwd"))
+        report[name] = dict(table_precision=over.get("table_precision", "fp32"),
+                            feature_precision=over.get("feature_precision", "fp32"), psnr_db=s.psnr(images[name]),
+                            hash_fwd_launch_ms=enc, mlp_fwd_launch_ms=mlp, all_launches_ms=sum(ms.values()),
+                            launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+        if name in twin:
+            report[name]["same_bits_as_unpacked_twin"] = bool(torch.equal(images[name].contiguous().view(torch.int32),
+                                                                          images[twin[name]].contiguous().view(torch.int32)))
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_unpacked_twin"] = float(np.median(times[name]) / np.median(times[base]))
+    write(a, s, report, grid_occupied_fraction={"geometry grid": geo.occupied_fraction(),
+                                                "default grid": default.occupied_fraction()})
+
+
 def opaque_setup(a, counts):
     """The scene trained afresh at each of `counts` in turn until the dense PSNR of the frame stops rising:
     (setup() of the chosen count, {count: dense PSNR})."""
@@ -498,10 +540,12 @@ def main():
     ap.add_argument("--mlp-precision", action="store_true", help="time the bf16 MLP forward (DESIGN.md §17)")
     ap.add_argument("--table-precision", action="store_true", help="time the fp16 hash tables (DESIGN.md §18)")
     ap.add_argument("--march-stop", action="store_true", help="time stopping rays inside the march (DESIGN.md §19)")
+    ap.add_argument("--feature-precision", action="store_true", help="time packed bf16 features (DESIGN.md §20)")
     ap.add_argument("--opaque-curve", default=None,
                     help="--march-stop: training iteration counts to try in turn until the dense PSNR stops rising")
     a = ap.parse_args()
-    mode, out = ((main_march_stop, "profiles/march_stop_render_time.json") if a.march_stop else
+    mode, out = ((main_feature_precision, "profiles/feat_bf16_render_time.json") if a.feature_precision else
+                 (main_march_stop, "profiles/march_stop_render_time.json") if a.march_stop else
                  (main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
                  (main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
                  (main_march, "profiles/march_render_time.json") if a.march else
