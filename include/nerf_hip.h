@@ -1005,6 +1005,52 @@ int nerf_slab_march_advance(const float* d_raw, const float* d_dist, const int32
                             const float* d_rays_d, int64_t n_rays, int64_t n_points, int64_t s1, float tau_max,
                             float* d_tau, uint8_t* d_alive, int32_t* d_stop, void* stream);
 
+/* ---- SH through a ray index in the grid march (csrc/march.hip, csrc/field_x6.hip) ----
+ * Additive entries (the ABI version stays 12). The view encoding of a march's point is its ray's: the list
+ * carries the ray's row number (int32, 4 B per point) and the MLP reads one 160-B record per ray through it,
+ * instead of a 64-B SH4 row per point.
+ *
+ * nerf_ray_sh_records: d_sh_rec [n_rays, 40] (16-B aligned) = for every packed ray row (n_cols must be 11), the
+ *   record nerf_sample_stratified_sh writes per ray: the 16 fp32 SH4 coefficients of the view direction (columns
+ *   8..10), then the three bf16 pieces of each (v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1); 16 x
+ *   piece 0, 16 x piece 1, 16 x piece 2), in every bit. 40 n_rays < 2^31. n_rays = 0 launches nothing and accepts
+ *   NULL buffers.
+ * nerf_rays_march_write, nerf_rays_slab_march_write: nerf_march_write and nerf_slab_march_write with
+ *   d_ray_c [capacity] (int32) in place of d_sh_c: entry idx receives the row number r of its ray in d_rays.
+ *   d_pts_c, d_z_c and d_dist_c are written as there, bit for bit, under the same capacity guard and the same
+ *   checks. No SH is evaluated; ray rows of 8 columns are accepted.
+ * nerf_mlp_fwd_rays, nerf_mlp_fwd_bf16_rays, nerf_mlp_fwd_bf16_pkbf_rays: the forwards of nerf_mlp_fwd_ord (no A-CAQ
+ *   record, geo output or calibration), nerf_mlp_fwd_bf16 and nerf_mlp_fwd_bf16_pkbf in the identity point order
+ *   with the SH of point p taken from record d_ray_of[p] (int32 [n_points]) of d_sh_rec [n_rays, 40] (16-B
+ *   aligned): the fp32-accurate forward uses the record's three pieces, the bf16 forwards piece 0. d_raw is, in
+ *   every bit, the twin's with sh_stride = 16 on the rows d_sh_rec[d_ray_of[p], 0..15]. There is no d_viewdirs
+ *   and no point order. Tail lanes read the last point's index. THE CALLER GUARANTEES 0 <= d_ray_of[p] < n_rays
+ *   for every p < n_points: the kernels cannot check it, and an index outside reads outside d_sh_rec.
+ *   n_points > 0 needs n_rays >= 1; 40 n_rays and the feature indexing stay below 2^31. n_points = 0 launches
+ *   nothing and accepts NULL per-point buffers (d_feat, d_ray_of, d_keep, d_raw) and a NULL d_sh_rec. */
+int nerf_ray_sh_records(const float* d_rays, int64_t n_rays, int n_cols, float* d_sh_rec, void* stream);
+int nerf_rays_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                          const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                          const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points, int64_t capacity,
+                          float* d_pts_c, float* d_z_c, float* d_dist_c, int32_t* d_ray_c, void* stream);
+int nerf_rays_slab_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                               int64_t k0, int64_t k1, const float* bbox_min, const float* bbox_max, int res,
+                               const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets,
+                               int64_t n_points, int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c,
+                               int32_t* d_ray_c, void* stream);
+int nerf_mlp_fwd_rays(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                      const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                      const uint8_t* d_keep, int64_t n_points,
+                      const nerf_mlp_weights* weights, float* d_raw, void* stream);
+int nerf_mlp_fwd_bf16_rays(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                           const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                           const uint8_t* d_keep, int64_t n_points,
+                           const nerf_mlp_weights* weights, float* d_raw, void* stream);
+int nerf_mlp_fwd_bf16_pkbf_rays(const uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                                const uint8_t* d_keep, int64_t n_points,
+                                const nerf_mlp_weights* weights, float* d_raw, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

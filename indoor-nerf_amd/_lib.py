@@ -271,6 +271,17 @@ SIGNATURES = {
     "nerf_slab_march_composite": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_int, c_int, c_vp, c_vp,
                                   c_vp, c_vp, c_vp, c_vp],
     "nerf_slab_march_advance": [c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, ctypes.c_float, c_vp, c_vp, c_vp, c_vp],
+    # SH through a ray index: the writes with d_ray_c in place of d_sh_c, the records, the forwards
+    "nerf_ray_sh_records": [c_vp, c_i64, c_int, c_vp, c_vp],
+    "nerf_rays_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_i64, c_i64,
+                              c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nerf_rays_slab_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_i64, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp,
+                                   c_vp, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp],
+    "nerf_mlp_fwd_rays": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights), c_vp, c_vp],
+    "nerf_mlp_fwd_bf16_rays": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights), c_vp,
+                               c_vp],
+    "nerf_mlp_fwd_bf16_pkbf_rays": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
+                                    c_vp, c_vp],
 }
 
 _lib = None

@@ -24,6 +24,8 @@ int launch_mlp_fwd_x6(const MlpArgs& a, hipStream_t stream);     // field_x6.hip
 int launch_mlp_act_minmax_x6(const MlpArgs& a, hipStream_t stream);
 int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream);
 int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_t stream);
+int launch_mlp_fwd_x6_rays(const MlpArgs& a, const int32_t* ray_ix, hipStream_t stream);
+int launch_mlp_fwd_bf16_rays(const MlpArgs& a, bool packed, const int32_t* ray_ix, hipStream_t stream);
 
 static int fill_args(MlpArgs& a, const float* d_feat, int64_t sp, int64_t sl, const float* d_sh, int64_t sh_stride,
                      const float* d_viewdirs, int64_t spr, const uint8_t* d_keep, int64_t n,
@@ -159,6 +161,52 @@ extern "C" int nerf_mlp_fwd_bf16_pkbf(const uint32_t* d_featw, int64_t feat_stri
     return mlp_fwd_bf16("mlp_fwd_bf16_pkbf", true, reinterpret_cast<const float*>(d_featw), feat_stride_point,
                         feat_stride_level, d_sh, sh_stride, d_viewdirs, samples_per_ray, d_keep, n_points, weights,
                         d_raw, order, stream);
+}
+
+// The three forwards reading SH through a ray index: point p uses record d_ray_of[p] of d_sh_rec
+// [n_rays, 40]; identity point order, no view directions, geo output, A-CAQ or saved h3. mode 0: the fp32-accurate x6
+// forward, 1: the bf16 forward, 2: the bf16 forward on packed bf16 features.
+static int mlp_fwd_rays(const char* who, int mode, const float* d_feat, int64_t feat_stride_point,
+                        int64_t feat_stride_level, const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                        const uint8_t* d_keep, int64_t n_points, const nerf_mlp_weights* w, float* d_raw, void* stream) {
+    NERF_REQUIRE(n_points >= 0 && n_rays >= 0, "%s: n_points %lld, n_rays %lld", who, (long long)n_points,
+                 (long long)n_rays);
+    NERF_REQUIRE(w && w->w0 && w->w1 && w->c0 && w->c1 && w->c2, "%s: null weight pointer", who);
+    if (n_points == 0) return NERF_OK;
+    NERF_REQUIRE(d_feat && d_sh_rec && d_ray_of && d_raw, "%s: null arg", who);
+    NERF_REQUIRE(n_rays >= 1, "%s: %lld points need n_rays >= 1", who, (long long)n_points);
+    NERF_REQUIRE((int64_t)kShRecord * n_rays < ((int64_t)1 << 31), "%s: %lld rays exceed 32-bit indexing", who,
+                 (long long)n_rays);
+    NERF_REQUIRE(((uintptr_t)d_sh_rec & 15) == 0, "%s: SH records must be 16-B aligned", who);
+    MlpArgs a{};
+    int rc = fill_args(a, d_feat, feat_stride_point, feat_stride_level, d_sh_rec, 0, nullptr, 1, d_keep, n_points, w);
+    if (rc) return rc;
+    a.raw = d_raw;
+    return mode == 0 ? launch_mlp_fwd_x6_rays(a, d_ray_of, as_stream(stream))
+                     : launch_mlp_fwd_bf16_rays(a, mode == 2, d_ray_of, as_stream(stream));
+}
+
+extern "C" int nerf_mlp_fwd_rays(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                                 const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays, const uint8_t* d_keep,
+                                 int64_t n_points, const nerf_mlp_weights* weights, float* d_raw, void* stream) {
+    return mlp_fwd_rays("mlp_fwd_rays", 0, d_feat, feat_stride_point, feat_stride_level, d_sh_rec, d_ray_of, n_rays,
+                        d_keep, n_points, weights, d_raw, stream);
+}
+
+extern "C" int nerf_mlp_fwd_bf16_rays(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,
+                                      const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                                      const uint8_t* d_keep, int64_t n_points, const nerf_mlp_weights* weights,
+                                      float* d_raw, void* stream) {
+    return mlp_fwd_rays("mlp_fwd_bf16_rays", 1, d_feat, feat_stride_point, feat_stride_level, d_sh_rec, d_ray_of, n_rays,
+                        d_keep, n_points, weights, d_raw, stream);
+}
+
+extern "C" int nerf_mlp_fwd_bf16_pkbf_rays(const uint32_t* d_featw, int64_t feat_stride_point,
+                                           int64_t feat_stride_level, const float* d_sh_rec, const int32_t* d_ray_of,
+                                           int64_t n_rays, const uint8_t* d_keep, int64_t n_points,
+                                           const nerf_mlp_weights* weights, float* d_raw, void* stream) {
+    return mlp_fwd_rays("mlp_fwd_bf16_pkbf_rays", 2, reinterpret_cast<const float*>(d_featw), feat_stride_point,
+                        feat_stride_level, d_sh_rec, d_ray_of, n_rays, d_keep, n_points, weights, d_raw, stream);
 }
 
 extern "C" int nerf_mlp_bwd_q(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,

@@ -351,6 +351,36 @@ __device__ __forceinline__ void load_in_x6(const MlpArgs& a, int64_t tile, int j
     in.SH = load_sh_split(a, in.pt, in.valid, h);
 }
 
+// SH through a ray index (the _rays forwards): point p's record is a.sh + kShRecord * ray_ix[p], the
+// record branch of load_sh_split / load_sh_bf16 with ray_of(a, pc) replaced by a 4-byte load. A ray's points are
+// consecutive in a march's list, so the 32 lanes of a tile read one or a few records: the lanes' 8-B loads below fall
+// into the same few cache lines, which the ray's other tiles find in the L2. The kernels cannot check
+// 0 <= ray_ix[p] < n_rays: the caller guarantees it. Tail lanes: the last point's (load_x6).
+__device__ __forceinline__ const uint16_t* ray_pieces(const MlpArgs& a, const int32_t* ray_ix, uint32_t pt, bool valid) {
+    const uint32_t pc = valid ? pt : (uint32_t)(a.P - 1);
+    return reinterpret_cast<const uint16_t*>(a.sh + (uint32_t)ray_ix[pc] * (uint32_t)kShRecord) + 32;
+}
+
+__device__ __forceinline__ S3 load_sh_split(const MlpArgs& a, uint32_t pt, bool valid, int h, const int32_t* ray_ix) {
+    const uint16_t* rec = ray_pieces(a, ray_ix, pt, valid);
+    S3 s;
+#pragma unroll
+    for (int q = 0; q < 3; ++q) {
+        const u32x2 g0 = *reinterpret_cast<const u32x2*>(rec + 16 * q + 4 * h);
+        const u32x2 g1 = *reinterpret_cast<const u32x2*>(rec + 16 * q + 8 + 4 * h);
+        s.p[q] = u32x4{g0.x, g0.y, g1.x, g1.y};
+    }
+    return s;
+}
+
+__device__ __forceinline__ void load_in_x6(const MlpArgs& a, int64_t tile, int j, int h, InX6& in,
+                                           const int32_t* ray_ix) {
+    in.pt = (uint32_t)(tile * 32 + j);
+    in.valid = tile * 32 + j < a.P;
+    load_x6(a, in.pt, in.valid, h, in.x, 0);
+    in.SH = load_sh_split(a, in.pt, in.valid, h, ray_ix);
+}
+
 // Row of point pt in raw / geo / graw / dgeo / dsh (MlpArgs point order)
 __device__ __forceinline__ uint32_t io_row(const MlpArgs& a, uint32_t pt) {
     return a.io_rows ? (uint32_t)a.io_rows[pt] : pt;
@@ -584,10 +614,12 @@ __device__ __forceinline__ uint32_t h3_off(int64_t tile, int t, int q, int lane)
 }
 
 // ================================================================ forward kernel
-template <bool QUANT>
+// RayIx: empty (the kernel as it was: the same parameter list, the same instructions), or one const int32_t*, the
+// ray index of nerf_mlp_fwd_rays, which selects the loaders that read the SH records through it
+template <bool QUANT, typename... RayIx>
 // 512-thread blocks: the 66.8 KB weight image is shared by 8 waves, so two blocks per CU give 4
 // waves per SIMD (105 VGPRs) instead of 2 with 256-thread blocks
-__global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a) {
+__global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a, RayIx... ray_ix) {
     __shared__ __attribute__((aligned(16))) __bf16 img[3 * IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
     fill_images(img, a.W);
@@ -600,7 +632,7 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a) {
     const int wpb = blockDim.x >> 6;
     for (int64_t tile = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * wpb) {
         InX6 in;
-        load_in_x6(a, tile, j, h, in);
+        load_in_x6(a, tile, j, h, in, ray_ix...);
         ActX6 f;
         const int z = opaque_zero();
         fwd_chain<QUANT>(img + z, in, f, lane, aq);
@@ -1315,6 +1347,17 @@ int launch_mlp_fwd_x6(const MlpArgs& a, hipStream_t stream) {
     return NERF_OK;
 }
 
+// nerf_mlp_fwd_rays: the x6 forward with the SH records read through ray_ix [a.P] (a.sh: the records, a.sh_stride 0)
+int launch_mlp_fwd_x6_rays(const MlpArgs& a, const int32_t* ray_ix, hipStream_t stream) {
+    NERF_REQUIRE(fits_u32(a), "mlp_fwd_rays: %lld points exceed 32-bit indexing", (long long)a.P);
+    const int64_t tiles = (a.P + 31) / 32;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
+    hipLaunchKernelGGL((mlp_fwd_x6_kernel<false, const int32_t*>), dim3((unsigned)blocks), dim3(512), 0, stream, a,
+                       ray_ix);
+    NERF_CHECK_LAUNCH("mlp_fwd_rays");
+    return NERF_OK;
+}
+
 int launch_mlp_act_minmax_x6(const MlpArgs& a, hipStream_t stream) {
     NERF_REQUIRE(fits_u32(a), "mlp_act_minmax(x6): %lld points exceed 32-bit indexing", (long long)a.P);
     const int64_t n = a.calib_points < a.P ? a.calib_points : a.P;
@@ -1443,6 +1486,14 @@ __device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, boo
     return pack_arr(shv);
 }
 
+// ... through a ray index (ray_pieces): piece 0 of the point's record
+__device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, bool valid, int h, const int32_t* ray_ix) {
+    const uint16_t* rec = ray_pieces(a, ray_ix, pt, valid);
+    const u32x2 g0 = *reinterpret_cast<const u32x2*>(rec + 4 * h);
+    const u32x2 g1 = *reinterpret_cast<const u32x2*>(rec + 8 + 4 * h);
+    return u32x4{g0.x, g0.y, g1.x, g1.y};
+}
+
 // Packed bf16 features (mlp_fwd_bf16_kernel<true>, nerf_mlp_fwd_bf16_pkbf): a.feat holds one word
 // {bf16 f0, bf16 f1} per (point, level), written by the packed encoder (hashgrid_pkbf.hip) with pk_bf16, a.sp / a.sl
 // in words. Lane (j, h) loads the words of levels 8c + 4q + 2h + e and uses them as they are:
@@ -1469,8 +1520,9 @@ __device__ __forceinline__ void load_x_pkbf(const MlpArgs& a, uint32_t pt, bool 
 // measured 37.7 us against 35.8 us per 786,432 points without it.
 // PK: the features are packed bf16 words (load_x_pkbf) and layer 0 takes them without a conversion; <false> is
 // the kernel as it was (the same instructions).
-template <bool PK>
-__global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
+// RayIx: as mlp_fwd_x6_kernel's: empty, or the ray index of nerf_mlp_fwd_bf16_rays / nerf_mlp_fwd_bf16_pkbf_rays.
+template <bool PK, typename... RayIx>
+__global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a, RayIx... ray_ix) {
     __shared__ __attribute__((aligned(16))) __bf16 img[IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
     fill_image_bf16(img, a.W);
@@ -1486,7 +1538,7 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a) {
         u32x4 xb[2];
         if constexpr (PK) load_x_pkbf(a, pt, valid, h, xb);
         else load_x6(a, pt, valid, h, x, 0);
-        const u32x4 SH = load_sh_bf16(a, pt, valid, h);
+        const u32x4 SH = load_sh_bf16(a, pt, valid, h, ray_ix...);
         const int z = opaque_zero();
         const __bf16* im = img + z;
         // layer 0: h1 = relu(W0 x)
@@ -1557,6 +1609,19 @@ int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream) {
     const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
     if (packed) hipLaunchKernelGGL(mlp_fwd_bf16_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
     else hipLaunchKernelGGL(mlp_fwd_bf16_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+    NERF_CHECK_LAUNCH(who);
+    return NERF_OK;
+}
+
+// nerf_mlp_fwd_bf16_rays / nerf_mlp_fwd_bf16_pkbf_rays: launch_mlp_fwd_bf16 with the SH records read through ray_ix
+int launch_mlp_fwd_bf16_rays(const MlpArgs& a, bool packed, const int32_t* ray_ix, hipStream_t stream) {
+    const char* who = packed ? "mlp_fwd_bf16_pkbf_rays" : "mlp_fwd_bf16_rays";
+    NERF_REQUIRE(fits_u32(a), "%s: %lld points exceed 32-bit indexing", who, (long long)a.P);
+    const int64_t tiles = (a.P + 31) / 32;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
+    const dim3 grid((unsigned)blocks), block(512);
+    if (packed) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, const int32_t*>), grid, block, 0, stream, a, ray_ix);
+    else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, const int32_t*>), grid, block, 0, stream, a, ray_ix);
     NERF_CHECK_LAUNCH(who);
     return NERF_OK;
 }

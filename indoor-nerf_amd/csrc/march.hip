@@ -40,6 +40,15 @@
 //     d = dist[e] * norm_d, s = sigma_e > 0 ? sigma_e : 0 (NaN gives 0), tau = tau + s * d; the ray dies
 //     (alive = 0, stop = s1) when tau > tau_max. early_stop.hip's rule with the packed dist in place of
 //     z[i + 1] - z[i]; a skipped lattice sample adds nothing, as a masked sigma does there.
+//
+// SH through a ray index: the view encoding is the same for every sample of a ray, so the list can
+// carry the ray's row number (4 B per point) instead of its SH4 row (64 B per point).
+//   nerf_ray_sh_records: one thread per packed ray row; the kShRecord record of the row's view direction (columns
+//     8..10): sh4_eval, 16 fp32 coefficients, then the three bf16 pieces of each. sampling.hip's
+//     sample_stratified_kernel writes the same record per ray; its lines are restated here (that file is on the
+//     training path and is not touched), and both files are built with -ffp-contract=off, so the bits agree.
+//   nerf_rays_march_write / nerf_rays_slab_march_write: march_write_kernel<true>: the write's walk with
+//     ray_c[idx] = r in place of the SH row; no SH is evaluated and rows of 8 columns are accepted.
 #include "compact_common.h"
 #include "occ_common.h"
 
@@ -67,6 +76,7 @@ struct MarchArgs {
     float* z_c;              // out [capacity]
     float* dist_c;           // out [capacity]
     float* sh_c;             // optional out [capacity, 16] (C == 11)
+    int32_t* ray_c;          // march_write_kernel<true>: out [capacity], the row number of the entry's ray
 };
 
 struct MarchRay {
@@ -166,6 +176,8 @@ __global__ void __launch_bounds__(kCompactThreads) march_offsets_kernel(MarchArg
     }
 }
 
+// kRays: the entry's ray index into ray_c instead of the ray's SH4 row into sh_c (<false> is the kernel as it was)
+template <bool kRays>
 __global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a) {
     const int lane = threadIdx.x & 63;
     const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
@@ -173,9 +185,11 @@ __global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a)
     if (a.counts[r] == 0) return;
     const MarchRay m = march_ray(a, r);
     float sh[16] = {};
-    if (a.sh_c) {
-        const float* v = a.rays + r * a.C + 8;
-        sh4_eval(v[0], v[1], v[2], sh);
+    if constexpr (!kRays) {
+        if (a.sh_c) {
+            const float* v = a.rays + r * a.C + 8;
+            sh4_eval(v[0], v[1], v[2], sh);
+        }
     }
     const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
     int64_t base = a.off[r];
@@ -190,13 +204,42 @@ __global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a)
             a.pts_c[3 * idx] = p[0]; a.pts_c[3 * idx + 1] = p[1]; a.pts_c[3 * idx + 2] = p[2];
             a.z_c[idx] = z;
             a.dist_c[idx] = k + 1 < a.K ? march_depth(m, a.t[k + 1]) - z : 1e10f;
-            if (a.sh_c) {
+            if constexpr (kRays) {
+                a.ray_c[idx] = (int32_t)r;
+            } else if (a.sh_c) {
                 float4* dst = reinterpret_cast<float4*>(a.sh_c + 16 * idx);
 #pragma unroll
                 for (int q = 0; q < 4; ++q) dst[q] = make_float4(sh[4 * q], sh[4 * q + 1], sh[4 * q + 2], sh[4 * q + 3]);
             }
         }
         base += __popcll(mask);
+    }
+}
+
+// ---------------------------------------------------------------- per-ray SH records
+// One thread per packed ray row: sampling.hip's record of the row's view direction (kShRecord floats: the 16 fp32
+// coefficients, then pieces 0, 1, 2 of the 16 as bf16), restated
+__global__ void __launch_bounds__(256) ray_sh_records_kernel(const float* __restrict__ rays, int64_t R, int C,
+                                                             float* __restrict__ rec) {
+    const int64_t r = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (r >= R) return;
+    const float* v = rays + r * C + 8;
+    float o[16];
+    sh4_eval(v[0], v[1], v[2], o);
+    float4* dst = reinterpret_cast<float4*>(rec + kShRecord * r);
+    dst[0] = make_float4(o[0], o[1], o[2], o[3]);
+    dst[1] = make_float4(o[4], o[5], o[6], o[7]);
+    dst[2] = make_float4(o[8], o[9], o[10], o[11]);
+    dst[3] = make_float4(o[12], o[13], o[14], o[15]);
+    __bf16* pc = reinterpret_cast<__bf16*>(rec + kShRecord * r + 16);
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {
+        const __bf16 p0 = (__bf16)o[k];
+        const float r1 = o[k] - (float)p0;
+        const __bf16 p1 = (__bf16)r1;
+        pc[k] = p0;
+        pc[16 + k] = p1;
+        pc[32 + k] = (__bf16)(r1 - (float)p1);
     }
 }
 
@@ -389,7 +432,8 @@ extern "C" int nerf_slab_march_count(const float* d_rays, int64_t n_rays, int n_
 static int march_write(const char* what, const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
                        int64_t n_samples, int64_t k0, int64_t k1, const float* bbox_min, const float* bbox_max, int res,
                        const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points,
-                       int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
+                       int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, bool index,
+                       int32_t* d_ray_c, void* stream) {
     MarchArgs a{};
     int rc = march_args(a, what, n_rays, n_cols, n_samples, k0, k1, bbox_min, bbox_max, res, false, nullptr, 0);
     if (rc) return rc;
@@ -402,11 +446,13 @@ static int march_write(const char* what, const float* d_rays, int64_t n_rays, in
                  what);
     NERF_REQUIRE(!d_sh_c || (n_cols == 11 && ((uintptr_t)d_sh_c & 15) == 0),
                  "%s: SH rows need ray rows of 11 columns and a 16-B aligned sh_c", what);
+    NERF_REQUIRE(!index || d_ray_c, "%s: null arg", what);
     a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = const_cast<int32_t*>(d_counts);
     a.off = const_cast<int32_t*>(d_offsets);
-    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c;
-    hipLaunchKernelGGL(march_write_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
-                       as_stream(stream), a);
+    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c; a.ray_c = d_ray_c;
+    const dim3 grid(blocks_for(n_rays, kMarchWaves)), block(kMarchThreads);
+    if (index) hipLaunchKernelGGL(march_write_kernel<true>, grid, block, 0, as_stream(stream), a);
+    else hipLaunchKernelGGL(march_write_kernel<false>, grid, block, 0, as_stream(stream), a);
     NERF_CHECK_LAUNCH(what);
     return NERF_OK;
 }
@@ -417,7 +463,7 @@ extern "C" int nerf_march_write(const float* d_rays, int64_t n_rays, int n_cols,
                                 float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
     return march_write("march_write", d_rays, n_rays, n_cols, d_t, n_samples, 0, n_samples > 0 ? n_samples : 0, bbox_min,
                        bbox_max, res, d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, d_sh_c,
-                       stream);
+                       false, nullptr, stream);
 }
 
 extern "C" int nerf_slab_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
@@ -426,7 +472,46 @@ extern "C" int nerf_slab_march_write(const float* d_rays, int64_t n_rays, int n_
                                      const int32_t* d_offsets, int64_t n_points, int64_t capacity, float* d_pts_c,
                                      float* d_z_c, float* d_dist_c, float* d_sh_c, void* stream) {
     return march_write("slab_march_write", d_rays, n_rays, n_cols, d_t, n_samples, k0, k1, bbox_min, bbox_max, res,
-                       d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, d_sh_c, stream);
+                       d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, d_sh_c, false, nullptr,
+                       stream);
+}
+
+// the two writes with a ray index in place of the SH rows (march_write_kernel<true>)
+extern "C" int nerf_rays_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                     int64_t n_samples, const float* bbox_min, const float* bbox_max, int res,
+                                     const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets,
+                                     int64_t n_points, int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c,
+                                     int32_t* d_ray_c, void* stream) {
+    return march_write("rays_march_write", d_rays, n_rays, n_cols, d_t, n_samples, 0, n_samples > 0 ? n_samples : 0,
+                       bbox_min, bbox_max, res, d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c,
+                       d_dist_c, nullptr, true, d_ray_c, stream);
+}
+
+extern "C" int nerf_rays_slab_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                          int64_t n_samples, int64_t k0, int64_t k1, const float* bbox_min,
+                                          const float* bbox_max, int res, const uint32_t* d_bits,
+                                          const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points,
+                                          int64_t capacity, float* d_pts_c, float* d_z_c, float* d_dist_c,
+                                          int32_t* d_ray_c, void* stream) {
+    return march_write("rays_slab_march_write", d_rays, n_rays, n_cols, d_t, n_samples, k0, k1, bbox_min, bbox_max, res,
+                       d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, nullptr, true, d_ray_c,
+                       stream);
+}
+
+// the kShRecord record of every packed ray row's view direction (ray_sh_records_kernel)
+extern "C" int nerf_ray_sh_records(const float* d_rays, int64_t n_rays, int n_cols, float* d_sh_rec, void* stream) {
+    NERF_REQUIRE(n_rays >= 0, "ray_sh_records: n_rays %lld", (long long)n_rays);
+    NERF_REQUIRE(n_cols == 11, "ray_sh_records: ray rows of %d columns (11: the view direction is columns 8..10)",
+                 n_cols);
+    NERF_REQUIRE((int64_t)kShRecord * n_rays < ((int64_t)1 << 31), "ray_sh_records: %lld rays exceed 32-bit indexing",
+                 (long long)n_rays);
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_sh_rec, "ray_sh_records: null arg");
+    NERF_REQUIRE(((uintptr_t)d_sh_rec & 15) == 0, "ray_sh_records: SH records must be 16-B aligned");
+    hipLaunchKernelGGL(ray_sh_records_kernel, dim3(blocks_for(n_rays, 256)), dim3(256), 0, as_stream(stream), d_rays,
+                       n_rays, n_cols, d_sh_rec);
+    NERF_CHECK_LAUNCH("ray_sh_records");
+    return NERF_OK;
 }
 
 // the checks the two compositing entries and the stopping rule share: the sizes and the packed list

@@ -247,19 +247,36 @@ class OccupancyGrid:
             n = int(offsets[R].item())     # one 4-byte host read sizes the list
         return rays, t, counts, offsets, rays_d, n
 
-    def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None):
-        """nerf_march_write of the list _march_count sized; with the same [k0, k1): nerf_slab_march_write."""
+    def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None, index=False):
+        """nerf_march_write of the list _march_count sized; with the same [k0, k1): nerf_slab_march_write.
+        index: the nerf_rays_ write; the fourth result is then ray_c int32 [n], the row of each
+        entry's ray in `rays`, and no SH row is formed."""
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
         f = dict(device=dev, dtype=torch.float32)
         pts_c, z_c, dist_c = torch.empty(n, 3, **f), torch.empty(n, **f), torch.empty(n, **f)
-        sh_c = torch.empty(n, 16, **f) if sh else None
+        if index:
+            last = torch.empty(n, device=dev, dtype=torch.int32)
+            last_ptr = _lib.ptr(last, "ray_c", torch.int32)
+        else:
+            last = torch.empty(n, 16, **f) if sh else None
+            last_ptr = _lib.ptr(last, "sh_c", allow_none=True)
         if n > 0:
             name, slab = ("nerf_march_write", ()) if k0 is None else ("nerf_slab_march_write", (int(k0), int(k1)))
-            _lib.call(name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab, self._bmin, self._bmax,
-                      self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
+            _lib.call(name.replace("nerf_", "nerf_rays_") if index else name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab,
+                      self._bmin, self._bmax, self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
                       _lib.ptr(offsets, "offsets", torch.int32), n, n, _lib.ptr(pts_c, "pts_c"), _lib.ptr(z_c, "z_c"),
-                      _lib.ptr(dist_c, "dist_c"), _lib.ptr(sh_c, "sh_c", allow_none=True), _lib.stream())
-        return pts_c, z_c, dist_c, sh_c
+                      _lib.ptr(dist_c, "dist_c"), last_ptr, _lib.stream())
+        return pts_c, z_c, dist_c, last
+
+    @staticmethod
+    def _ray_sh_records(rays):
+        """nerf_ray_sh_records: the SH record [R, 40] of every packed ray row [R, 11]."""
+        R = rays.shape[0]
+        rec = torch.empty(R, 40, device=rays.device, dtype=torch.float32)
+        if R > 0:
+            _lib.call("nerf_ray_sh_records", _lib.ptr(rays, "rays"), R, rays.shape[1], _lib.ptr(rec, "sh_rec"),
+                      _lib.stream())
+        return rec
 
     def march(self, rays, K):
         """The samples of packed ray rows [R, 8 or 11] that lie in occupied cells, out of K lattice samples per

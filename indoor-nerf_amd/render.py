@@ -433,7 +433,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
-                table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None):
+                table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None, march_sh=None):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -473,7 +473,16 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     (nerf_hash_encode_fwd_pkbf, with fp16 tables nerf_hash_encode_fwd_half_pkbf) and every MLP forward launch read
     those words (nerf_mlp_fwd_bf16_pkbf): the rounding the bf16 MLP does first, done by the encoder, so the result is
     bit for bit the mlp_precision="bf16" render at half the feature bytes. Composes with occupancy=, early_stop=,
-    march=, march_stop=, table_precision= and render's ray_bounds=. None and "fp32" are the call without it."""
+    march=, march_stop=, table_precision= and render's ray_bounds=. None and "fp32" are the call without it.
+    march_sh (None, "rows" or "rays"; with march=): "rays" makes the march's list carry each point's ray
+    index (4 B) instead of its SH4 row (64 B); one SH record per ray is formed once per chunk (nerf_ray_sh_records) and
+    the MLP reads it through the index (the _rays entry of the call's precision). The result is bit for bit the march
+    without it, in every entry. Composes with march_stop=, mlp_precision=, table_precision=, feature_precision= and
+    render's ray_bounds=. None and "rows" are the call without it: the same launches, the same buffers."""
+    by_ray = False
+    if march_sh is not None:
+        from .sparse_field import check_march_sh
+        by_ray = check_march_sh(march_sh, march, "render_rays")
     half = False
     if table_precision is not None:
         from .sparse_field import check_table_nets, check_table_precision
@@ -499,7 +508,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
                                   bf16=bf16, half=half, march_stop=march_stop, march_stop_slab=march_stop_slab,
-                                  packed=packed)
+                                  packed=packed, by_ray=by_ray)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -643,20 +652,30 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
                        predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False,
-                       march_stop=None, march_stop_slab=128, packed=False):
+                       march_stop=None, march_stop_slab=128, packed=False, by_ray=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing. With march_stop the same in slabs
-    (_march_slabs)."""
+    (_march_slabs). by_ray (march_sh="rays"): the write leaves a ray index in place
+    of the SH rows, and the field reads the SH records of the chunk's packed rays through it."""
     run_fn = network_fn if network_fine is None else network_fine
     K, stop = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
                            predict_normals, occupancy, early_stop, march_stop, march_stop_slab)
     if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
         raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
 
+    records = []   # by_ray: the SH records of the chunk's packed rays, formed before its first field call
+
     def field(rays, pts_c, sh_c):
-        """The field on a packed list of n > 0 points."""
+        """The field on a packed list of n > 0 points (by_ray: sh_c is the points' ray index into `rays`, the same
+        packed rows in every slab of a chunk)."""
         from .sparse_field import MarchRequest
-        req = pts_c._nerf_sparse = MarchRequest(sh_c, march_points)
+        if by_ray:
+            if not records:
+                records.append(grid._ray_sh_records(rays))
+            req = MarchRequest(None, march_points, ray_c=sh_c, sh_rec=records[0])
+        else:
+            req = MarchRequest(sh_c, march_points)
+        pts_c._nerf_sparse = req
         raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half, packed)
         del pts_c._nerf_sparse
         if not req.used:   # a foreign query function ignores the attribute: never fall back silently
@@ -664,13 +683,13 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
         return raw
 
     if stop is not None:
-        ret = _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw)
+        ret = _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw, by_ray)
         if DEBUG:
             check_numerics(ret)
         return ret
     rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K)
     R, dev = rays.shape[0], rays.device
-    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True)
+    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, index=by_ray)
     grid._last = (n, R * K)
     f = dict(device=dev, dtype=torch.float32)
     raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
@@ -689,11 +708,12 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     return ret
 
 
-def _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw):
+def _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw, by_ray=False):
     """The march of _render_rays_march with march_stop = stop = (eps, slab): the lattice front to
     back in slabs; per slab the packed list of the rays alive (one 4-byte host read sizes it), field(rays, pts_c,
     sh_c) on it, its compositing into the per-ray state and, unless it is the last, the stopping rule. A slab with
-    an empty list skips the field and its launches (the last slab's compositing always runs: it writes the maps)."""
+    an empty list skips the field and its launches (the last slab's compositing always runs: it writes the maps).
+    by_ray: every slab's write leaves the ray index in place of the SH rows."""
     from .early_stop import tau_max_of
     eps, Ks = stop
     tau_max = tau_max_of(eps)
@@ -713,7 +733,7 @@ def _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw):
                 tau, alive = torch.zeros(R, **f), torch.ones(R, device=dev, dtype=torch.uint8)
                 state = torch.empty(R, 6, device=dev, dtype=torch.float64)
             stops = torch.full((R,), K, device=dev, dtype=torch.int32)
-        pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, k0, k1)
+        pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, k0, k1, index=by_ray)
         raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
         evaluated += n
         counts_all.append(counts)
@@ -907,7 +927,11 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
     spans its own [near', far']. mlp_precision and table_precision go to
     render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
-    §20). retraw is refused with march: the packed entries of several chunks do not concatenate."""
+    §20) and march_sh. retraw is refused with march: the packed entries of several chunks do not
+    concatenate."""
+    if kwargs.get("march_sh") is not None:   # also when no chunk reaches render_rays
+        from .sparse_field import check_march_sh
+        check_march_sh(kwargs["march_sh"], kwargs.get("march"), "render")
     if kwargs.get("march_stop") is not None:   # also when no chunk reaches render_rays
         from .sparse_field import check_march_stop
         check_march_stop(kwargs["march_stop"], kwargs.get("march_stop_slab", 128), kwargs.get("march"), "render")

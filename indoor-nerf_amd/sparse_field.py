@@ -20,7 +20,8 @@ NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop"
                    "march": "rays are not marched in training", "ray_bounds": "rays are not bounded in training",
                    "mlp_precision": "the backward recomputes the forward in fp32",
                    "table_precision": "the backward scatters into the fp32 tables",
-                   "feature_precision": "the backward reads fp32 features"}
+                   "feature_precision": "the backward reads fp32 features",
+                   "march_sh": "the backward reads per-point SH rows"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -43,11 +44,16 @@ class SparseRequest:
 class MarchRequest:
     """render_rays' request of a grid march (attached to the packed point tensor [n, 3] as `pts._nerf_sparse`):
     the SH4 rows of the points' rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch.
+    With march_sh="rays"  sh_c is None and the request carries the points' ray index, ray_c int32 [n],
+    and one SH record per ray, sh_rec [R, 40] (0 <= ray_c < R: the march's write guarantees it).
     run_network sets `used`, as for a SparseRequest."""
     what = "march"
 
-    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS):
+    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None):
+        if (sh_c is None) == (ray_c is None) or (ray_c is None) != (sh_rec is None):
+            raise ValueError("march: a request carries either sh_c or (ray_c, sh_rec)")
         self.sh_c, self.max_points = sh_c, check_march_points(max_points)
+        self.ray_c, self.sh_rec = ray_c, sh_rec
         self.used = False
 
 
@@ -126,10 +132,20 @@ def feature_buffer(mlp, n, device):
     return torch.empty(2 * n, device=device, dtype=torch.float32), 2, torch.float32
 
 
-def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order):
+def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order, rays=None):
     """The MLP launch of the sparse field calls: n points with level-major features (level stride sl; packed: in
     words, point stride 1) and SH rows at stride 16 -> their rows of raw (order: a nerf_point_order or None); mlp:
-    the call's MlpRequest or None."""
+    the call's MlpRequest or None. rays = (ray index pointer, SH records pointer, number of records) instead of
+    sh_c (march_sh="rays"; identity order): the _rays entry of the same precision."""
+    if rays is not None:
+        if sh_c is not None or order is not None:
+            raise ValueError("march_sh: a ray index replaces the SH rows and has no point order")
+        ray_of, sh_rec, n_rays = rays
+        name = "nerf_mlp_fwd_bf16_pkbf_rays" if is_packed(mlp) else ("nerf_mlp_fwd_bf16_rays" if mlp is not None else
+                                                                     "nerf_mlp_fwd_rays")
+        _lib.call(name, feat, 1 if is_packed(mlp) else 2, sl, sh_rec, ray_of, n_rays, keep, n, weights, raw,
+                  _lib.stream())
+        return
     front = (feat, 1 if is_packed(mlp) else 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
     if is_packed(mlp):
         _lib.call("nerf_mlp_fwd_bf16_pkbf", *front, order, _lib.stream())
@@ -216,6 +232,20 @@ def check_march_stop(march_stop, march_stop_slab, march, prefix):
     return float(march_stop), int(march_stop_slab)
 
 
+def check_march_sh(value, march, prefix):
+    """march_sh of `prefix` (render_rays, render) -> whether the march's list carries a ray index instead of SH rows
+    (DESIGN.md §21); its refusals, one fixed sentence each: an unknown value, "rays" without march=, gradients
+    enabled."""
+    if value is None or (isinstance(value, str) and value == "rows"):
+        return False
+    if not (isinstance(value, str) and value == "rays"):
+        raise ValueError(f"{prefix}: march_sh must be None, 'rows' or 'rays', got {value!r}")
+    if march is None:
+        raise ValueError(f"{prefix}: march_sh='rays' needs march= (the ray index belongs to a grid march's list)")
+    check_forward_only("march_sh", prefix)
+    return True
+
+
 def check_forward_only(what, prefix, raw_noise_std=0.):
     """The refusals every forward-only keyword `what` of `prefix` (render_rays, render) shares: no gradients, no
     raw noise."""
@@ -243,14 +273,19 @@ def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embe
 
 def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None, tab=None):
     """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
-    raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16) run over the list in
-    slices of at most req.max_points points; a point's result does not depend on its slice. mlp, tab: the call's
+    raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16, or with a request by ray index
+    the slice of the index and the whole of the records) run over the list in slices of at most req.max_points points; a point's result does not depend on its slice. mlp, tab: the call's
     MlpRequest and TableRequest, or None."""
     from .field import _weights_struct
-    _begin_field_call("march", inputs.dim() == 2 and req.sh_c is not None, "packed inputs [n, 3]", viewdirs, fn,
-                      embed_fn, embeddirs_fn)
+    by_ray = req.ray_c is not None
+    _begin_field_call("march", inputs.dim() == 2 and (by_ray or req.sh_c is not None), "packed inputs [n, 3]", viewdirs,
+                      fn, embed_fn, embeddirs_fn)
     n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
-    if tuple(req.sh_c.shape) != (n, 16):
+    if by_ray:
+        if tuple(req.ray_c.shape) != (n,) or req.sh_rec.dim() != 2 or req.sh_rec.shape[1] != 40:
+            raise ValueError("march: ray index / SH records of the request do not match the points")
+        sh_rec, n_rec = _lib.ptr(req.sh_rec, "sh_rec"), req.sh_rec.shape[0]
+    elif tuple(req.sh_c.shape) != (n, 16):
         raise ValueError("march: SH rows of the request do not match the points")
     f = dict(device=dev, dtype=torch.float32)
     raw = torch.empty(n, 4, **f)
@@ -264,8 +299,9 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
         k = min(m, n - s0)
         embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * w], w, w * k, keep[:k], half=tab is not None,
                              packed=is_packed(mlp))
-        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * k, _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
-                    _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None)
+        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * k, None if by_ray else _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
+                    _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None,
+                    (_lib.ptr_at(req.ray_c, s0, "ray_c", torch.int32), sh_rec, n_rec) if by_ray else None)
     return raw
 
 

@@ -13,7 +13,12 @@ points with the features hot (written once, the two launches alternate) and at 6
 resident in cache (each timed launch follows an encode launch of that size into its buffer: 805 MB of fp32
 features, 403 MB of words). Median and min in us per launch, the ratio of the medians, whether raw has the same bits.
 --counter-run (with --feature-precision): a few launch pairs and nothing else, to run under the profiler's counter
-collection on its own. --out FILE also writes the JSON."""
+collection on its own. --out FILE also writes the JSON.
+
+--march-sh: only the A/B of the three forwards on per-point SH rows (nerf_mlp_fwd_ord, nerf_mlp_fwd_bf16,
+nerf_mlp_fwd_bf16_pkbf at sh_stride 16) against the same forwards reading one SH record per ray through a ray index
+(nerf_mlp_fwd_rays, nerf_mlp_fwd_bf16_rays, nerf_mlp_fwd_bf16_pkbf_rays), segments of 49 consecutive
+points per ray, at the same two point counts and cache states as --feature-precision. --counter-run applies."""
 import argparse
 import ctypes
 import json
@@ -160,15 +165,108 @@ def packed_ab(dev, counter_run=False, rounds=5, per_round=20):
     return out
 
 
+def march_sh_ab(dev, counter_run=False, rounds=5, per_round=20, segment=49):
+    """The --march-sh table: see the module docstring."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    from tables import blender_bbox
+    lo, hi = blender_bbox()
+    emb = nerf.HashEmbedder((torch.from_numpy(lo), torch.from_numpy(hi)), finest_resolution=1024).to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(0)
+    net = nerf.NeRFSmall(2, 64, 15, 3, 64, 32, 16).to(dev)
+    w = _lib.MlpWeights(*[_lib.ptr(p.detach()).value for p in net.mlp_weights()])
+    with torch.no_grad():
+        for e in emb.embeddings:
+            e.weight.copy_((torch.rand(e.weight.shape, device=dev, generator=g) * 2 - 1) * 0.05)
+    L = emb.n_levels
+    out = {}
+    for R, S, cold in ((4096, 64, False), (32768, 192, True)):
+        P = R * S
+        o = 4.0 * torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        d = torch.nn.functional.normalize(-o + 0.8 * torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        t = torch.linspace(2.0, 6.0, S, device=dev)
+        pts = (o[:, None] + d[:, None] * t[None, :, None]).reshape(-1, 3).contiguous()
+        n_rays = -(-P // segment)
+        ray_of = (torch.arange(P, device=dev) // segment).to(torch.int32)
+        views = torch.nn.functional.normalize(torch.randn(n_rays, 3, device=dev, generator=g), dim=-1)
+        rays = torch.cat([torch.zeros(n_rays, 8, device=dev), views], 1).contiguous()
+        rec = torch.empty(n_rays, 40, device=dev)
+        _lib.call("nerf_ray_sh_records", _lib.ptr(rays), n_rays, 11, _lib.ptr(rec), _lib.stream())
+        sh_c = rec[ray_of.long(), :16].contiguous()
+        feat, words = torch.empty(L, P, 2, device=dev), torch.empty(L, P, device=dev, dtype=torch.int32)
+        keep = torch.empty(P, device=dev, dtype=torch.bool)
+        kp, wp = _lib.ptr(keep, dtype=torch.bool), ctypes.byref(w)
+        rows_view = (_lib.ptr(sh_c), 16, None, 1, kp, P, wp)
+        rays_view = (_lib.ptr(rec), _lib.ptr(ray_of, dtype=torch.int32), n_rays, kp, P, wp)
+        fp, wdp = (_lib.ptr(feat), 2, 2 * P), (_lib.ptr(words, dtype=torch.int32), 1, P)
+        raws = {}
+
+        def fn(entry, front, view, tail):
+            raws[entry] = torch.empty(P, 4, device=dev)
+            return lambda: _lib.call(entry, *front, *view, _lib.ptr(raws[entry]), *tail, _lib.stream())
+        fns = {"nerf_mlp_fwd_ord": fn("nerf_mlp_fwd_ord", fp, rows_view, (None, None, None, 0, None)),
+               "nerf_mlp_fwd_rays": fn("nerf_mlp_fwd_rays", fp, rays_view, ()),
+               "nerf_mlp_fwd_bf16": fn("nerf_mlp_fwd_bf16", fp, rows_view, (None,)),
+               "nerf_mlp_fwd_bf16_rays": fn("nerf_mlp_fwd_bf16_rays", fp, rays_view, ()),
+               "nerf_mlp_fwd_bf16_pkbf": fn("nerf_mlp_fwd_bf16_pkbf", wdp, rows_view, (None,)),
+               "nerf_mlp_fwd_bf16_pkbf_rays": fn("nerf_mlp_fwd_bf16_pkbf_rays", wdp, rays_view, ())}
+        with torch.no_grad():
+            encode = {False: lambda: emb.encode_into(pts, feat, 2, 2 * P, keep),
+                      True: lambda: emb.encode_into(pts, words, 1, P, keep, packed=True)}
+            enc = {name: encode["pkbf" in name] for name in fns}
+            for name in fns:
+                enc[name]()
+                fns[name]()
+            torch.cuda.synchronize()
+            if counter_run:
+                for _ in range(3):
+                    for name in fns:
+                        if cold:
+                            enc[name]()
+                        fns[name]()
+                torch.cuda.synchronize()
+                continue
+            ts = {name: [] for name in fns}
+            for _ in range(rounds):
+                for f in fns.values():
+                    for _ in range(3):
+                        f()
+                torch.cuda.synchronize()
+                for _ in range(per_round if not cold else max(4, per_round // 2)):
+                    for name, f in fns.items():
+                        if cold:      # the features written by a preceding encode of this size, as in a frame
+                            enc[name]()
+                        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        e0.record()
+                        f()
+                        e1.record()
+                        torch.cuda.synchronize()
+                        ts[name].append(e0.elapsed_time(e1))
+        row = {name + "_us_median": round(float(np.median(v)) * 1e3, 1) for name, v in ts.items()}
+        row.update({name + "_us_min": round(float(np.min(v)) * 1e3, 1) for name, v in ts.items()})
+        for twin in ("nerf_mlp_fwd_ord", "nerf_mlp_fwd_bf16", "nerf_mlp_fwd_bf16_pkbf"):
+            by_ray = twin.replace("_ord", "") + "_rays"
+            row[f"{twin}_over_{by_ray}"] = round(float(np.median(ts[twin]) / np.median(ts[by_ray])), 3)
+            row[f"{by_ray}_raw_same_bits"] = bool(torch.equal(raws[twin].view(torch.int32), raws[by_ray].view(torch.int32)))
+        row["features"] = "written by a preceding encode launch" if cold else "hot"
+        row["sh_bytes"] = {"rows": sh_c.numel() * 4, "index + records": ray_of.numel() * 4 + rec.numel() * 4}
+        out[str(P)] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--march-sh", action="store_true")
     ap.add_argument("--feature-precision", action="store_true")
     ap.add_argument("--counter-run", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    if a.feature_precision:
-        report = {"device": torch.cuda.get_device_name(0), "packed_ab": packed_ab(dev, a.counter_run)}
+    if a.feature_precision or a.march_sh:
+        report = {"device": torch.cuda.get_device_name(0)}
+        if a.march_sh:
+            report["march_sh_ab"] = march_sh_ab(dev, a.counter_run)
+        else:
+            report["packed_ab"] = packed_ab(dev, a.counter_run)
         if a.out:
             os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
             with open(a.out, "w") as fp:

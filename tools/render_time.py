@@ -455,6 +455,46 @@ def main_feature_precision(a):
                                                 "default grid": default.occupied_fraction()})
 
 
+def main_march_sh(a):
+    """The march_sh table: the march at K = 192 and 512 through both grids, with the fp32-accurate MLP,
+    the bf16 MLP and the bf16 MLP on packed features, each without and with march_sh="rays"; the pair must give the
+    same image bit for bit. Per row also the time of its write launches and of its MLP launches in one untimed frame."""
+    s = setup(a)
+    grids = {f"{kind} grid": s.new_grid(kind) for kind in ("geometry", "default")}
+    precisions = (("", {}), (", bf16 MLP", dict(mlp_precision="bf16")),
+                  (", bf16 MLP, bf16 features", dict(mlp_precision="bf16", feature_precision="bf16")))
+    variants, twin = [("dense", {})], {}      # the fp32 dense frame: measure()'s reference for speedup_vs_dense
+    for gname, grid in grids.items():
+        for K in (192, 512):
+            for pname, pover in precisions:
+                base = f"{gname}: march, K = {K}{pname}"
+                over = dict(march=grid, march_samples=K, **pover)
+                variants += [(base, over), (base + ", SH by ray", dict(over, march_sh="rays"))]
+                twin[base + ", SH by ray"] = base
+
+    report, images = {}, {}
+    for name, over in variants:         # untimed frames: PSNR, evaluated points, and where the launches' time goes
+        out = s.frame(over)
+        images[name] = out[0]
+        ms = launch_times(s, over)
+        report[name] = dict(march_sh=over.get("march_sh", "rows"), psnr_db=s.psnr(images[name]),
+                            march_write_launch_ms=sum(v for k, v in ms.items() if "march_write" in k),
+                            mlp_fwd_launch_ms=sum(v for k, v in ms.items() if k.startswith("nerf_mlp_fwd")),
+                            sh_records_launch_ms=ms.get("nerf_ray_sh_records", 0.0), all_launches_ms=sum(ms.values()),
+                            launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+        if "march" in over:
+            report[name]["evaluated_points"] = int(out[3]["march_samples"].sum())
+        if name in twin:
+            report[name]["same_bits_as_rows_twin"] = bool(torch.equal(images[name].contiguous().view(torch.int32),
+                                                                      images[twin[name]].contiguous().view(torch.int32)))
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_rows_twin"] = float(np.median(times[name]) / np.median(times[base]))
+        for k in (name, base):
+            report[k]["ns_per_evaluated_point"] = float(np.median(times[k]) * 1e6 / max(1, report[k]["evaluated_points"]))
+    write(a, s, report, grid_occupied_fraction={k: g.occupied_fraction() for k, g in grids.items()})
+
+
 def opaque_setup(a, counts):
     """The scene trained afresh at each of `counts` in turn until the dense PSNR of the frame stops rising:
     (setup() of the chosen count, {count: dense PSNR})."""
@@ -541,10 +581,12 @@ def main():
     ap.add_argument("--table-precision", action="store_true", help="time the fp16 hash tables (DESIGN.md §18)")
     ap.add_argument("--march-stop", action="store_true", help="time stopping rays inside the march (DESIGN.md §19)")
     ap.add_argument("--feature-precision", action="store_true", help="time packed bf16 features (DESIGN.md §20)")
+    ap.add_argument("--march-sh", action="store_true", help="time SH read through a ray index (DESIGN.md §21)")
     ap.add_argument("--opaque-curve", default=None,
                     help="--march-stop: training iteration counts to try in turn until the dense PSNR stops rising")
     a = ap.parse_args()
-    mode, out = ((main_feature_precision, "profiles/feat_bf16_render_time.json") if a.feature_precision else
+    mode, out = ((main_march_sh, "profiles/march_sh_render_time.json") if a.march_sh else
+                 (main_feature_precision, "profiles/feat_bf16_render_time.json") if a.feature_precision else
                  (main_march_stop, "profiles/march_stop_render_time.json") if a.march_stop else
                  (main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
                  (main_mlp_precision, "profiles/mlp_bf16_render_time.json") if a.mlp_precision else
