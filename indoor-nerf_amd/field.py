@@ -15,6 +15,7 @@ import torch.nn as nn
 from . import _lib
 from .hashgrid import HashEmbedder, SHEncoder, accumulate_grad_buffers, bin_chunks, hash_encode_bwd, pending_bins
 from .quantization import LearnedBitwidthQuantizer, calibrate_from_stats, new_stats, quant_records
+from .sparse_field import level_features
 
 
 def _weights_struct(weights, w0q=None):
@@ -190,11 +191,9 @@ class FieldFn(torch.autograd.Function):
             raise NotImplementedError("run_network: gradients w.r.t. positions/directions are not implemented")
         n_tab = embedder.n_levels
         tables, weights, head = params[:n_tab], params[n_tab:n_tab + 5], params[n_tab + 5:]
-        mlp = getattr(pts, "_nerf_mlp", None)
-        bf16 = mlp is not None                               # run_network's checked MlpRequest
-        packed = bf16 and mlp.packed                         # its packed bf16 features
-        w = 1 if packed else 2                               # elements of feat per (point, level) entry
-        half = getattr(pts, "_nerf_tab", None) is not None   # and its checked TableRequest
+        req = getattr(pts, "_nerf_req", None)   # run_network's checked FieldRequest: §17, §20, §18
+        bf16, packed, half = (req.bf16, req.packed, req.half) if req is not None else (False, False, False)
+        w = 1 if packed else 2                  # elements of feat per (point, level) entry
         pts = pts.contiguous()
         sh_rays = getattr(viewdirs, "_nerf_sh", None)   # render_rays' per-ray SH4 rows (sh_stride 0)
         viewdirs = viewdirs.contiguous()
@@ -223,9 +222,7 @@ class FieldFn(torch.autograd.Function):
             reuse.record(pts, embedder, tables)
             ctx.reuse = ("coarse", reuse)
         else:
-            feat = (torch.empty(n_tab, P, device=dev, dtype=torch.int32) if packed
-                    else torch.empty(n_tab, P, 2, device=dev, dtype=torch.float32))
-            keep, row0 = torch.empty(P, device=dev, dtype=torch.bool), 0
+            feat, keep, row0 = level_features(n_tab, P, dev, packed), torch.empty(P, device=dev, dtype=torch.bool), 0
             embedder.encode_into(pts, feat, w, w * P, keep, half=half, packed=packed)
         sl = w * feat.shape[1]
         keep = keep[row0:row0 + P]                   # the MLP's keep flags, in its point order
@@ -658,22 +655,17 @@ def batchify(fn, chunk):
 def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64):
     """run_nerf.py:53-68. inputs [..., S, 3], viewdirs [R, 3]. Fused when the modules are ours;
     netchunk is then only a memory knob the fused kernels do not need."""
-    sparse = getattr(inputs, "_nerf_sparse", None)   # sparse_field.SparseRequest of this render_rays call
-    mlp = getattr(inputs, "_nerf_mlp", None)         # sparse_field.MlpRequest of it (mlp_precision="bf16")
-    tab = getattr(inputs, "_nerf_tab", None)         # sparse_field.TableRequest of it (table_precision="fp16")
-    if mlp is not None:
-        mlp.used = True
-    if tab is not None:
-        tab.used = True
-    if sparse is not None:
-        from .sparse_field import run_network_sparse
-        sparse.used = True
-        return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, sparse, mlp, tab)
+    req = getattr(inputs, "_nerf_req", None)   # sparse_field.FieldRequest of this field call (DESIGN.md §22)
+    if req is not None:
+        req.used = True                        # before any refusal: the query function did reach this package
+        if req.what is not None:
+            from .sparse_field import run_network_sparse
+            return run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req)
     call_ok = isinstance(embeddirs_fn, SHEncoder) and viewdirs is not None and inputs.dim() == 3
-    if mlp is not None:   # never the eager path below, and never fp32 silently
+    if req is not None and req.bf16:   # never the eager path below, and never fp32 silently
         from .sparse_field import check_mlp_field
         check_mlp_field(call_ok, "inputs [R, S, 3]", fn, embed_fn)
-    if tab is not None:   # likewise: never the eager path, never the fp32 tables silently
+    if req is not None and req.half:   # likewise: never the eager path, never the fp32 tables silently
         from .sparse_field import check_table_field
         check_table_field(call_ok, "inputs [R, S, 3]", fn, embed_fn)
     fused = isinstance(embed_fn, HashEmbedder) and isinstance(fn, NeRFSmall) and call_ok
@@ -683,15 +675,9 @@ def run_network(inputs, viewdirs, fn, embed_fn, embeddirs_fn, netchunk=1024 * 64
         R, S = inputs.shape[0], inputs.shape[1]
         reuse = getattr(inputs, "_nerf_reuse", None)     # render.CoarseReuse of this render_rays call
         flat = inputs.reshape(-1, 3)
-        if mlp is not None:
-            flat._nerf_mlp = mlp
-        if tab is not None:
-            flat._nerf_tab = tab
+        if req is not None:
+            flat._nerf_req = req      # on this call's own view of the points, for FieldFn.forward
         raw = FieldFn.apply(flat, viewdirs, S, embed_fn, fn, netchunk, reuse, *embed_fn.tables(), *fn.field_params())
-        if mlp is not None:
-            del flat._nerf_mlp
-        if tab is not None:
-            del flat._nerf_tab
         out = raw.reshape(R, S, fn.raw_channels)
         # without a normals head FieldFn's backward only queues its job: raw2outputs may then defer the
         # compositing backward too (render.CompositeJob)

@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, sparse_field
 from .hashgrid import early_tv
 
 img2mse = lambda x, y: torch.mean((x - y) ** 2)  # noqa: E731
@@ -334,8 +334,7 @@ class CoarseReuse:
         """The shared feature / keep buffers; returns them and the coarse pass's first row. packed: the features as
         bf16 words [L, P] int32 (feature_precision="bf16")."""
         P = self.R * (self.S + self.N)
-        self.feat = (torch.empty(n_levels, P, device=device, dtype=torch.int32) if packed
-                     else torch.empty(n_levels, P, 2, device=device, dtype=torch.float32))
+        self.feat = sparse_field.level_features(n_levels, P, device, packed)
         self.keep = torch.empty(P, device=device, dtype=torch.bool)
         return self.feat, self.keep, self.R * self.N
 
@@ -376,49 +375,19 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
     return out
 
 
-def _query_tab(network_query_fn, pts, viewdirs, fn, half):
-    """network_query_fn(pts, viewdirs, fn); half: with a TableRequest on the points (table_precision="fp16")."""
-    if not half:
-        return network_query_fn(pts, viewdirs, fn)
-    from .sparse_field import TableRequest
-    req = pts._nerf_tab = TableRequest()
+def _query(network_query_fn, pts, viewdirs, fn, req=None):
+    """The field call of one pass -> (raw, stops). req: its sparse_field.FieldRequest, which rides on the points as
+    `pts._nerf_req` for the length of the call (the only place that attaches one), or None: the plain
+    call, nothing attached. stops: int32 [R] with early ray termination (early_stop.py), None otherwise."""
+    if req is None:
+        return network_query_fn(pts, viewdirs, fn), None
+    pts._nerf_req = req
     try:
         raw = network_query_fn(pts, viewdirs, fn)
     finally:
-        del pts._nerf_tab
-    if not req.used:   # a foreign query function ignores the attribute: never read the fp32 tables silently
-        raise ValueError("render_rays: table_precision needs a network_query_fn that calls this package's run_network")
-    return raw
-
-
-def _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half=False, packed=False):
-    """network_query_fn(pts, viewdirs, fn); bf16: with an MlpRequest on the points (mlp_precision="bf16"), packed:
-    one that asks for packed bf16 features (feature_precision="bf16"); half: with a TableRequest beside it
-    (_query_tab)."""
-    if not bf16:
-        return _query_tab(network_query_fn, pts, viewdirs, fn, half)
-    from .sparse_field import MlpRequest
-    req = pts._nerf_mlp = MlpRequest(packed=packed)
-    try:
-        raw = _query_tab(network_query_fn, pts, viewdirs, fn, half)
-    finally:
-        del pts._nerf_mlp
-    if not req.used:   # a foreign query function ignores the attribute: never render in fp32 silently
-        raise ValueError("render_rays: mlp_precision needs a network_query_fn that calls this package's run_network")
-    return raw
-
-
-def _query(network_query_fn, pts, viewdirs, fn, occupancy, early=None, bf16=False, half=False, packed=False):
-    """The field call of one pass -> (raw, stops): early = (z, rays_d, eps, slab) of early ray termination
-    (stops int32 [R], early_stop.py), None otherwise (stops None)."""
-    if occupancy is None and early is None:
-        return _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half, packed), None
-    from .sparse_field import SparseRequest
-    req = pts._nerf_sparse = SparseRequest(occupancy, early)
-    raw = _query_mlp(network_query_fn, pts, viewdirs, fn, bf16, half, packed)
-    del pts._nerf_sparse
-    if not req.used:   # a foreign query function ignores the attribute: never fall back to the dense path silently
-        raise ValueError(f"render_rays: {req.what} needs a network_query_fn that calls this package's run_network")
+        del pts._nerf_req
+    if not req.used:   # a foreign query function ignores the attribute: never fall back to another path silently
+        raise ValueError(f"render_rays: {req.blame} needs a network_query_fn that calls this package's run_network")
     return raw, req.stop
 
 
@@ -479,43 +448,24 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     the MLP reads it through the index (the _rays entry of the call's precision). The result is bit for bit the march
     without it, in every entry. Composes with march_stop=, mlp_precision=, table_precision=, feature_precision= and
     render's ray_bounds=. None and "rows" are the call without it: the same launches, the same buffers."""
-    by_ray = False
-    if march_sh is not None:
-        from .sparse_field import check_march_sh
-        by_ray = check_march_sh(march_sh, march, "render_rays")
-    half = False
-    if table_precision is not None:
-        from .sparse_field import check_table_nets, check_table_precision
-        half = check_table_precision(table_precision, "render_rays")
-    if half:
-        check_table_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn)
-    bf16 = False
-    if mlp_precision is not None:
-        from .sparse_field import check_mlp_nets, check_mlp_precision
-        bf16 = check_mlp_precision(mlp_precision, "render_rays")
-    if bf16:
-        check_mlp_nets([network_fn] + ([] if network_fine is None else [network_fine]), embed_fn, predict_normals)
-    packed = False
-    if feature_precision is not None:
-        from .sparse_field import check_feature_precision
-        packed = check_feature_precision(feature_precision, bf16, "render_rays")
-    if march_stop is not None and march is None:
-        from .sparse_field import check_march_stop
-        check_march_stop(march_stop, march_stop_slab, march, "render_rays")
+    opts = sparse_field.field_options("render_rays", march, march_sh, march_stop, march_stop_slab, mlp_precision,
+                                      table_precision, feature_precision)
+    nets = [network_fn] + ([] if network_fine is None else [network_fine])
+    if opts.half:
+        sparse_field.check_table_nets(nets, embed_fn)
+    if opts.bf16:
+        sparse_field.check_mlp_nets(nets, embed_fn, predict_normals)
     if march is not None:
-        return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points,
+        return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points, opts,
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
-                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  bf16=bf16, half=half, march_stop=march_stop, march_stop_slab=march_stop_slab,
-                                  packed=packed, by_ray=by_ray)
+                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
         early = check_params(early_stop, early_stop_slab)
     if early is not None or occupancy is not None:
-        from .sparse_field import check_forward_only
-        check_forward_only("occupancy" if early is None else "early_stop", "render_rays", raw_noise_std)
+        sparse_field.check_forward_only("occupancy" if early is None else "early_stop", "render_rays", raw_noise_std)
     rays = ray_batch.detach().float().contiguous()
     R, C = rays.shape
     dev = rays.device
@@ -546,8 +496,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
              if (N_importance > 0 and _REUSE["on"] and R > 0 and occupancy is None and early is None) else None)
     if reuse is not None:
         pts._nerf_reuse = reuse       # the fused run_network records the coarse encoding in it
-    raw, stops = _query(network_query_fn, pts, viewdirs, network_fn, occupancy,
-                        None if early is None else (z, rays_d) + early, bf16, half, packed)
+    raw, stops = _query(network_query_fn, pts, viewdirs, network_fn,
+                        opts.request(occupancy, None if early is None else (z, rays_d) + early))
     if reuse is not None:
         del pts._nerf_reuse
         if reuse.state != "recorded" or R * (N_samples + N_importance) > 2 ** 31 - 1:
@@ -588,8 +538,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         if reuse is not None:
             pts._nerf_reuse = reuse
         stops0 = stops
-        raw, stops = _query(network_query_fn, pts, viewdirs, run_fn, occupancy,
-                            None if early is None else (z, rays_d) + early, bf16, half, packed)
+        raw, stops = _query(network_query_fn, pts, viewdirs, run_fn,
+                            opts.request(occupancy, None if early is None else (z, rays_d) + early))
         if reuse is not None:
             del pts._nerf_reuse
             reuse.release_forward()
@@ -625,11 +575,10 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
 
 
 def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, perturb, raw_noise_std, predict_normals,
-                 occupancy, early_stop, march_stop=None, march_stop_slab=128):
-    """render_rays' refusals with march=, all before any launch -> (K, (eps, slab) of march_stop or None)."""
+                 occupancy, early_stop):
+    """render_rays' refusals with march= after field_options', all before any launch -> K."""
     from .occupancy import OccupancyGrid, _check_modules, check_march_samples
-    from .sparse_field import check_forward_only, check_march_points, check_march_stop
-    stop = check_march_stop(march_stop, march_stop_slab, grid, "render_rays")
+    from .sparse_field import check_forward_only, check_march_points
     if not isinstance(grid, OccupancyGrid):
         raise ValueError(f"render_rays: march must be an OccupancyGrid, got {type(grid).__name__}")
     K = check_march_samples(march_samples, "render_rays: march")
@@ -646,44 +595,38 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
         raise ValueError("render_rays: march does not support predict_normals or a normals head")
     if embed_fn is not None:
         _check_modules(embed_fn, fn, "render_rays: march")
-    return K, stop
+    return K
 
 
-def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, embed_fn=None,
+def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, opts, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None, bf16=False, half=False,
-                       march_stop=None, march_stop_slab=128, packed=False, by_ray=False):
+                       predict_normals=False, occupancy=None, early_stop=None):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
-    the list (sparse_field.run_network_packed), the packed compositing. With march_stop the same in slabs
-    (_march_slabs). by_ray (march_sh="rays"): the write leaves a ray index in place
-    of the SH rows, and the field reads the SH records of the chunk's packed rays through it."""
+    the list (sparse_field.run_network_packed), the packed compositing. opts: the call's FieldOptions. With
+    opts.stop (march_stop) the same in slabs (_march_slabs). opts.by_ray (march_sh="rays", DESIGN.md
+    §21): the write leaves a ray index in place of the SH rows, and the field reads the SH records of the chunk's
+    packed rays through it."""
     run_fn = network_fn if network_fine is None else network_fine
-    K, stop = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
-                           predict_normals, occupancy, early_stop, march_stop, march_stop_slab)
+    K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
+                     predict_normals, occupancy, early_stop)
     if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
         raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
-
+    by_ray = opts.by_ray
     records = []   # by_ray: the SH records of the chunk's packed rays, formed before its first field call
 
     def field(rays, pts_c, sh_c):
         """The field on a packed list of n > 0 points (by_ray: sh_c is the points' ray index into `rays`, the same
         packed rows in every slab of a chunk)."""
-        from .sparse_field import MarchRequest
         if by_ray:
             if not records:
                 records.append(grid._ray_sh_records(rays))
-            req = MarchRequest(None, march_points, ray_c=sh_c, sh_rec=records[0])
+            march = sparse_field.MarchList(None, march_points, ray_c=sh_c, sh_rec=records[0])
         else:
-            req = MarchRequest(sh_c, march_points)
-        pts_c._nerf_sparse = req
-        raw = _query_mlp(network_query_fn, pts_c, rays[:, 8:11], run_fn, bf16, half, packed)
-        del pts_c._nerf_sparse
-        if not req.used:   # a foreign query function ignores the attribute: never fall back silently
-            raise ValueError("render_rays: march needs a network_query_fn that calls this package's run_network")
-        return raw
+            march = sparse_field.MarchList(sh_c, march_points)
+        return _query(network_query_fn, pts_c, rays[:, 8:11], run_fn, opts.request(march=march))[0]
 
-    if stop is not None:
-        ret = _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw, by_ray)
+    if opts.stop is not None:
+        ret = _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw)
         if DEBUG:
             check_numerics(ret)
         return ret
@@ -708,14 +651,14 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     return ret
 
 
-def _march_slabs(ray_batch, grid, K, stop, field, white_bkgd, retraw, by_ray=False):
-    """The march of _render_rays_march with march_stop = stop = (eps, slab): the lattice front to
+def _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw):
+    """The march of _render_rays_march with march_stop, opts.stop = (eps, slab): the lattice front to
     back in slabs; per slab the packed list of the rays alive (one 4-byte host read sizes it), field(rays, pts_c,
     sh_c) on it, its compositing into the per-ray state and, unless it is the last, the stopping rule. A slab with
     an empty list skips the field and its launches (the last slab's compositing always runs: it writes the maps).
-    by_ray: every slab's write leaves the ray index in place of the SH rows."""
+    opts.by_ray: every slab's write leaves the ray index in place of the SH rows."""
     from .early_stop import tau_max_of
-    eps, Ks = stop
+    (eps, Ks), by_ray = opts.stop, opts.by_ray
     tau_max = tau_max_of(eps)
     rays = tau = alive = stops = state = rays_d = None
     rgb_map = depth_map = acc_map = None
@@ -929,29 +872,18 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
     §20) and march_sh. retraw is refused with march: the packed entries of several chunks do not
     concatenate."""
-    if kwargs.get("march_sh") is not None:   # also when no chunk reaches render_rays
-        from .sparse_field import check_march_sh
-        check_march_sh(kwargs["march_sh"], kwargs.get("march"), "render")
-    if kwargs.get("march_stop") is not None:   # also when no chunk reaches render_rays
-        from .sparse_field import check_march_stop
-        check_march_stop(kwargs["march_stop"], kwargs.get("march_stop_slab", 128), kwargs.get("march"), "render")
+    # render_rays' value checks, also when no chunk reaches it (ray_bounds with every ray missed)
+    opts = sparse_field.field_options("render", kwargs.get("march"), kwargs.get("march_sh"), kwargs.get("march_stop"),
+                                      kwargs.get("march_stop_slab", 128), kwargs.get("mlp_precision"),
+                                      kwargs.get("table_precision"), kwargs.get("feature_precision"))
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")
     if ray_bounds is not None:
         _check_ray_bounds(ray_bounds)
-    bf16 = False
-    if kwargs.get("mlp_precision") is not None:   # also when no chunk reaches render_rays (ray_bounds with every ray missed)
-        from .sparse_field import check_mlp_precision
-        bf16 = check_mlp_precision(kwargs["mlp_precision"], "render")
-    if kwargs.get("feature_precision") is not None:   # likewise
-        from .sparse_field import check_feature_precision
-        check_feature_precision(kwargs["feature_precision"], bf16, "render")
-    if kwargs.get("table_precision") is not None:   # likewise
-        from .sparse_field import check_table_nets, check_table_precision
-        if check_table_precision(kwargs["table_precision"], "render"):
-            nets = [kwargs[k] for k in ("network_fn", "network_fine") if kwargs.get(k) is not None]
-            check_table_nets(nets, kwargs.get("embed_fn"), "render")
+    if opts.half:
+        nets = [kwargs[k] for k in ("network_fn", "network_fine") if kwargs.get(k) is not None]
+        sparse_field.check_table_nets(nets, kwargs.get("embed_fn"), "render")
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, K, c2w)
     else:

@@ -1,12 +1,15 @@
 """The field call of the forward-only render paths that evaluate only some samples: an occupancy grid
 (occupancy.py), early ray termination (early_stop.py), or both; and the field
-call of a grid march over its packed list of kept samples (MarchRequest).
+call of a grid march over its packed list of kept samples (MarchList). Also the one request
+that carries every forward-only keyword to the field (FieldOptions, FieldRequest).
 
-render_rays attaches a SparseRequest to the point tensor of a pass; the fused run_network (field.py) hands
-the call to run_network_sparse. The kept samples are compacted in ascending order
+render_rays attaches a FieldRequest to the point tensor of a pass; the fused run_network (field.py) hands
+a sparse call to run_network_sparse. The kept samples are compacted in ascending order
 (csrc/sparse_points.hip), hash-encoded and run through the MLP, whose results land in their rows of raw;
 every other sample gets an all-zero raw row, which compositing gives weight 0 exactly.
 """
+import typing
+
 import numpy as np
 import torch
 
@@ -25,49 +28,80 @@ NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop"
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
-class SparseRequest:
-    """render_rays' request on its way to the fused run_network (attached to the point tensor as
-    `pts._nerf_sparse`): the occupancy grid or None, and early = (z [R, S], rays_d [R, 3], eps, slab) of
-    early ray termination or None. run_network sets `used` (a foreign query function leaves it False and
-    render_rays raises) and, with early, `stop` (int32 [R]: leading samples for which the ray was alive)."""
+class FieldOptions(typing.NamedTuple):
+    """What the call-level keywords of one render_rays / render call ask of its field calls (field_options builds it):
+    bf16 (mlp_precision="bf16"), half (table_precision="fp16", §18), packed (feature_precision="bf16",
+    §20), by_ray (march_sh="rays", §21) and stop = (eps, slab) of march_stop or None (§19)."""
+    bf16: bool = False
+    half: bool = False
+    packed: bool = False
+    by_ray: bool = False
+    stop: typing.Optional[tuple] = None
 
-    def __init__(self, grid=None, early=None):
-        self.grid, self.early = grid, early
-        self.used, self.stop = False, None
-
-    @property
-    def what(self):
-        """The keyword the request's messages name."""
-        return "occupancy" if self.early is None else "early_stop"
+    def request(self, grid=None, early=None, march=None):
+        """The FieldRequest of one field call under these options, or None when the call asks for nothing (the
+        default path: nothing is built, nothing rides on the points)."""
+        if grid is None and early is None and march is None and not (self.bf16 or self.half):
+            return None
+        return FieldRequest(grid, early, march, self.bf16, self.half, self.packed)
 
 
-class MarchRequest:
-    """render_rays' request of a grid march (attached to the packed point tensor [n, 3] as `pts._nerf_sparse`):
-    the SH4 rows of the points' rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch.
-    With march_sh="rays"  sh_c is None and the request carries the points' ray index, ray_c int32 [n],
-    and one SH record per ray, sh_rec [R, 40] (0 <= ray_c < R: the march's write guarantees it).
-    run_network sets `used`, as for a SparseRequest."""
-    what = "march"
+class MarchList:
+    """The packed list of a grid march's field call (FieldRequest.march): the SH4 rows of the points'
+    rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch. With march_sh="rays" 
+    sh_c is None and the list carries the points' ray index, ray_c int32 [n], and one SH record per ray, sh_rec
+    [R, 40] (0 <= ray_c < R: the march's write guarantees it)."""
 
     def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None):
         if (sh_c is None) == (ray_c is None) or (ray_c is None) != (sh_rec is None):
             raise ValueError("march: a request carries either sh_c or (ray_c, sh_rec)")
         self.sh_c, self.max_points = sh_c, check_march_points(max_points)
         self.ray_c, self.sh_rec = ray_c, sh_rec
-        self.used = False
 
 
-class MlpRequest:
-    """render_rays' request of the bf16 MLP forward (mlp_precision="bf16"), attached to the point
-    tensor of every pass as `pts._nerf_mlp`, beside a SparseRequest / MarchRequest when there is one. run_network
-    sets `used` (a foreign query function leaves it False and render_rays raises) and routes every MLP forward
-    launch of the call to nerf_mlp_fwd_bf16. packed (feature_precision="bf16"): the feature buffers
-    of the call hold one word {bf16 f0, bf16 f1} per (point, level); every hash-encoding launch then goes to the
-    _pkbf entry of its tables and every MLP forward launch to nerf_mlp_fwd_bf16_pkbf."""
-    what = "mlp_precision"
+class FieldRequest:
+    """One field call of a forward-only render on its way from render_rays to the fused run_network (field.py),
+    attached to the point tensor as `pts._nerf_req` by render._query alone: the occupancy grid or
+    None; early = (z [R, S], rays_d [R, 3], eps, slab) of early ray termination or None; march, the MarchList of a
+    grid march's packed points [n, 3], or None; bf16, half, packed as in FieldOptions. run_network sets `used` (a
+    foreign query function leaves it False and render._query raises) and, with early, `stop` (int32 [R]: leading
+    samples for which the ray was alive)."""
 
-    def __init__(self, packed=False):
-        self.used, self.packed = False, bool(packed)
+    def __init__(self, grid=None, early=None, march=None, bf16=False, half=False, packed=False):
+        if packed and not bf16:
+            raise ValueError("field request: packed bf16 features need the bf16 MLP")
+        if march is not None and (grid is not None or early is not None):
+            raise ValueError("field request: a march's list does not combine with a grid or early termination")
+        self.grid, self.early, self.march = grid, early, march
+        self.bf16, self.half, self.packed = bool(bf16), bool(half), bool(packed)
+        self.used, self.stop = False, None
+
+    @property
+    def what(self):
+        """The keyword of the sparse field call the request asks for; None: the dense call."""
+        if self.march is not None:
+            return "march"
+        if self.early is not None:
+            return "early_stop"
+        return None if self.grid is None else "occupancy"
+
+    @property
+    def blame(self):
+        """The keyword that render._query's refusal of a foreign query function names."""
+        return "table_precision" if self.half else "mlp_precision" if self.bf16 else self.what
+
+
+def field_options(prefix, march, march_sh, march_stop, march_stop_slab, mlp_precision, table_precision,
+                  feature_precision):
+    """The value checks of the call-level forward-only keywords of `prefix` (render_rays, render), in one fixed
+    order -> FieldOptions. The checks that need the call's modules (check_table_nets, check_mlp_nets) follow in the
+    caller."""
+    by_ray = check_march_sh(march_sh, march, prefix)
+    stop = check_march_stop(march_stop, march_stop_slab, march, prefix)
+    bf16 = check_mlp_precision(mlp_precision, prefix)
+    packed = check_feature_precision(feature_precision, bf16, prefix)
+    half = check_table_precision(table_precision, prefix)
+    return FieldOptions(bf16, half, packed, by_ray, stop)
 
 
 def check_mlp_precision(value, prefix):
@@ -92,9 +126,9 @@ def check_mlp_nets(nets, embed_fn, predict_normals, prefix="render_rays"):
 
 
 def check_mlp_field(call_ok, shape_words, fn, embed_fn):
-    """The dense run_network's refusals for an MlpRequest, all before any launch (call_ok: SHEncoder view
+    """The dense run_network's refusals for a request with bf16, all before any launch (call_ok: SHEncoder view
     encoding, viewdirs and the inputs that shape_words describes), in _begin_field_call's order."""
-    what = MlpRequest.what
+    what = "mlp_precision"
     if not call_ok:
         raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
     _check_modules(embed_fn, fn, what)
@@ -119,51 +153,45 @@ def check_feature_precision(value, mlp_bf16, prefix):
     return True
 
 
-def is_packed(mlp):
-    """Whether the field call of MlpRequest `mlp` (or None) keeps packed bf16 features."""
-    return mlp is not None and mlp.packed
+def is_packed(req):
+    """Whether the field call of FieldRequest `req` (or None) keeps packed bf16 features."""
+    return req is not None and req.packed
 
 
-def feature_buffer(mlp, n, device):
-    """An uninitialised flat feature buffer of n (point, level) entries for the field call of MlpRequest `mlp` (or
+def feature_buffer(req, n, device):
+    """An uninitialised flat feature buffer of n (point, level) entries for the field call of FieldRequest `req` (or
     None) -> (buffer, w, dtype): w elements per entry, 2 float32 or, packed, 1 int32 word (half the bytes)."""
-    if is_packed(mlp):
+    if is_packed(req):
         return torch.empty(n, device=device, dtype=torch.int32), 1, torch.int32
     return torch.empty(2 * n, device=device, dtype=torch.float32), 2, torch.float32
 
 
-def mlp_forward(mlp, feat, sl, sh_c, keep, n, weights, raw, order, rays=None):
+def level_features(n_levels, P, device, packed=False):
+    """The dense field call's uninitialised feature buffer of P points (FieldFn.forward, render.CoarseReuse):
+    [L, P, 2] float32 or, packed, one bf16 word pair per entry, [L, P] int32."""
+    if packed:
+        return torch.empty(n_levels, P, device=device, dtype=torch.int32)
+    return torch.empty(n_levels, P, 2, device=device, dtype=torch.float32)
+
+
+def mlp_forward(req, feat, sl, sh_c, keep, n, weights, raw, order, rays=None):
     """The MLP launch of the sparse field calls: n points with level-major features (level stride sl; packed: in
-    words, point stride 1) and SH rows at stride 16 -> their rows of raw (order: a nerf_point_order or None); mlp:
-    the call's MlpRequest or None. rays = (ray index pointer, SH records pointer, number of records) instead of
+    words, point stride 1) and SH rows at stride 16 -> their rows of raw (order: a nerf_point_order or None); req:
+    the call's FieldRequest or None. rays = (ray index pointer, SH records pointer, number of records) instead of
     sh_c (march_sh="rays"; identity order): the _rays entry of the same precision."""
+    bf16, packed = req is not None and req.bf16, is_packed(req)
     if rays is not None:
         if sh_c is not None or order is not None:
             raise ValueError("march_sh: a ray index replaces the SH rows and has no point order")
         ray_of, sh_rec, n_rays = rays
-        name = "nerf_mlp_fwd_bf16_pkbf_rays" if is_packed(mlp) else ("nerf_mlp_fwd_bf16_rays" if mlp is not None else
-                                                                     "nerf_mlp_fwd_rays")
-        _lib.call(name, feat, 1 if is_packed(mlp) else 2, sl, sh_rec, ray_of, n_rays, keep, n, weights, raw,
-                  _lib.stream())
+        name = "nerf_mlp_fwd_bf16_pkbf_rays" if packed else "nerf_mlp_fwd_bf16_rays" if bf16 else "nerf_mlp_fwd_rays"
+        _lib.call(name, feat, 1 if packed else 2, sl, sh_rec, ray_of, n_rays, keep, n, weights, raw, _lib.stream())
         return
-    front = (feat, 1 if is_packed(mlp) else 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
-    if is_packed(mlp):
-        _lib.call("nerf_mlp_fwd_bf16_pkbf", *front, order, _lib.stream())
-    elif mlp is not None:
-        _lib.call("nerf_mlp_fwd_bf16", *front, order, _lib.stream())
+    front = (feat, 1 if packed else 2, sl, sh_c, 16, None, 1, keep, n, weights, raw)
+    if bf16:
+        _lib.call("nerf_mlp_fwd_bf16_pkbf" if packed else "nerf_mlp_fwd_bf16", *front, order, _lib.stream())
     else:
         _lib.call("nerf_mlp_fwd_ord", *front, None, None, None, 0, order, _lib.stream())
-
-
-class TableRequest:
-    """render_rays' request of the fp16 hash tables (table_precision="fp16"), attached to the point
-    tensor of every pass as `pts._nerf_tab`, beside an MlpRequest and a SparseRequest / MarchRequest when there are
-    any. run_network sets `used` (a foreign query function leaves it False and render_rays raises) and routes every
-    hash-encoding launch of the call to nerf_hash_encode_fwd_half (HashEmbedder.encode_into(half=True))."""
-    what = "table_precision"
-
-    def __init__(self):
-        self.used = False
 
 
 def check_table_precision(value, prefix):
@@ -198,9 +226,9 @@ def check_table_nets(nets, embed_fn, prefix="render_rays"):
 
 
 def check_table_field(call_ok, shape_words, fn, embed_fn):
-    """The dense run_network's refusals for a TableRequest, all before any launch (call_ok: SHEncoder view
+    """The dense run_network's refusals for a request with half, all before any launch (call_ok: SHEncoder view
     encoding, viewdirs and the inputs that shape_words describes)."""
-    what = TableRequest.what
+    what = "table_precision"
     if not call_ok:
         raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
     _check_table_modules(embed_fn, fn, what)
@@ -271,21 +299,21 @@ def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embe
         embed_fn.current_step += 1
 
 
-def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None, tab=None):
-    """run_network (field.py) for a MarchRequest: inputs [n, 3], the packed kept samples of a march ->
-    raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16, or with a request by ray index
-    the slice of the index and the whole of the records) run over the list in slices of at most req.max_points points; a point's result does not depend on its slice. mlp, tab: the call's
-    MlpRequest and TableRequest, or None."""
+def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+    """run_network (field.py) for a FieldRequest with a MarchList: inputs [n, 3], the packed kept samples of a
+    march -> raw [n, 4]. The hash encoding and the MLP (identity order, SH rows at stride 16, or with a list by ray
+    index the slice of the index and the whole of the records) run over the list in slices of at most max_points
+    points; a point's result does not depend on its slice."""
     from .field import _weights_struct
-    by_ray = req.ray_c is not None
-    _begin_field_call("march", inputs.dim() == 2 and (by_ray or req.sh_c is not None), "packed inputs [n, 3]", viewdirs,
-                      fn, embed_fn, embeddirs_fn)
+    ml = req.march
+    by_ray = ml.ray_c is not None
+    _begin_field_call("march", inputs.dim() == 2, "packed inputs [n, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
     n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
     if by_ray:
-        if tuple(req.ray_c.shape) != (n,) or req.sh_rec.dim() != 2 or req.sh_rec.shape[1] != 40:
+        if tuple(ml.ray_c.shape) != (n,) or ml.sh_rec.dim() != 2 or ml.sh_rec.shape[1] != 40:
             raise ValueError("march: ray index / SH records of the request do not match the points")
-        sh_rec, n_rec = _lib.ptr(req.sh_rec, "sh_rec"), req.sh_rec.shape[0]
-    elif tuple(req.sh_c.shape) != (n, 16):
+        sh_rec, n_rec = _lib.ptr(ml.sh_rec, "sh_rec"), ml.sh_rec.shape[0]
+    elif tuple(ml.sh_c.shape) != (n, 16):
         raise ValueError("march: SH rows of the request do not match the points")
     f = dict(device=dev, dtype=torch.float32)
     raw = torch.empty(n, 4, **f)
@@ -293,25 +321,24 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
         return raw
     pts = inputs.detach().float().contiguous()
     weights = _weights_struct(fn.mlp_weights())
-    m = min(n, req.max_points)
-    (feat, w, fdt), keep = feature_buffer(mlp, L * m, dev), torch.empty(m, device=dev, dtype=torch.bool)
+    m = min(n, ml.max_points)
+    (feat, w, fdt), keep = feature_buffer(req, L * m, dev), torch.empty(m, device=dev, dtype=torch.bool)
     for s0 in range(0, n, m):
         k = min(m, n - s0)
-        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * w], w, w * k, keep[:k], half=tab is not None,
-                             packed=is_packed(mlp))
-        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * k, None if by_ray else _lib.ptr_at(req.sh_c, 16 * s0, "sh_c"),
+        embed_fn.encode_into(pts[s0:s0 + k], feat[:L * k * w], w, w * k, keep[:k], half=req.half, packed=req.packed)
+        mlp_forward(req, _lib.ptr(feat, "feat", fdt), w * k, None if by_ray else _lib.ptr_at(ml.sh_c, 16 * s0, "sh_c"),
                     _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None,
-                    (_lib.ptr_at(req.ray_c, s0, "ray_c", torch.int32), sh_rec, n_rec) if by_ray else None)
+                    (_lib.ptr_at(ml.ray_c, s0, "ray_c", torch.int32), sh_rec, n_rec) if by_ray else None)
     return raw
 
 
-def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=None, tab=None):
-    """run_network (field.py) for a SparseRequest: inputs [R, S, 3], viewdirs [R, 3] -> raw [R, S, 4] with
-    the field evaluated at the kept samples only and zero rows elsewhere. Without early termination the call
-    is one slab through req.grid.compact; with it, slabs of req.early's size front to back, nerf_ert_advance
-    between them, and req.stop receives the stops."""
-    if isinstance(req, MarchRequest):
-        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp, tab)
+def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
+    """run_network (field.py) for a FieldRequest whose `what` is set: inputs [R, S, 3], viewdirs [R, 3] ->
+    raw [R, S, 4] with the field evaluated at the kept samples only and zero rows elsewhere (a march's list goes to
+    run_network_packed). Without early termination the call is one slab through req.grid.compact; with it, slabs of
+    req.early's size front to back, nerf_ert_advance between them, and req.stop receives the stops."""
+    if req.march is not None:
+        return run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req)
     from .field import _point_order, _weights_struct
     what = req.what
     _begin_field_call(what, inputs.dim() == 3, "inputs [R, S, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
@@ -332,12 +359,12 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     raw = torch.empty(P, 4, **f)
     weights = _weights_struct(fn.mlp_weights())
 
-    _, w, fdt = feature_buffer(mlp, 0, dev)   # elements per (point, level) entry of the call's feature buffers
+    _, w, fdt = feature_buffer(req, 0, dev)   # elements per (point, level) entry of the call's feature buffers
 
     def field(n, rows, pts_c, sh_c, feat, keep):
         """The field at the n compacted points; rows of raw `rows` receive the results."""
-        embed_fn.encode_into(pts_c, feat, w, w * n, keep, half=tab is not None, packed=is_packed(mlp))
-        mlp_forward(mlp, _lib.ptr(feat, "feat", fdt), w * n, _lib.ptr(sh_c, "sh_c"),
+        embed_fn.encode_into(pts_c, feat, w, w * n, keep, half=req.half, packed=req.packed)
+        mlp_forward(req, _lib.ptr(feat, "feat", fdt), w * n, _lib.ptr(sh_c, "sh_c"),
                     _lib.ptr(keep, "keep", torch.bool), n, weights, _lib.ptr(raw, "raw"), _point_order((rows, 0, 0)))
 
     if req.early is None:
@@ -345,7 +372,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
         rows, pts_c, sh_c = req.grid.compact(pts, viewdirs, S, raw)
         n = rows.shape[0]
         if n > 0:
-            field(n, rows, pts_c, sh_c, feature_buffer(mlp, L * n, dev)[0], torch.empty(n, device=dev, dtype=torch.bool))
+            field(n, rows, pts_c, sh_c, feature_buffer(req, L * n, dev)[0], torch.empty(n, device=dev, dtype=torch.bool))
         return raw.reshape(R, S, 4)
 
     z, rays_d = z.detach().float().contiguous(), rays_d.detach().float().contiguous()
@@ -363,7 +390,7 @@ def run_network_sparse(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req, mlp=No
     count = torch.empty(1, **i32)
     ws = torch.empty(int(_lib.load().nerf_ert_compact_workspace_bytes(cap)) // 4, **i32)
     rows, pts_c, sh_c = torch.empty(cap, **i32), torch.empty(cap, 3, **f), torch.empty(cap, 16, **f)
-    feat, keep = feature_buffer(mlp, L * cap, dev)[0], torch.empty(cap, device=dev, dtype=torch.bool)
+    feat, keep = feature_buffer(req, L * cap, dev)[0], torch.empty(cap, device=dev, dtype=torch.bool)
     evaluated = 0
 
     def compact(s0, s1, stages, n):

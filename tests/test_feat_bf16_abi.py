@@ -58,8 +58,9 @@ def test_python_keywords(nerf):
     assert inspect.signature(nerf.render_rays).parameters["feature_precision"].default is None
     assert inspect.signature(nerf.HashEmbedder.encode_into).parameters["packed"].default is False
     from indoor_nerf_amd import sparse_field
-    assert inspect.signature(sparse_field.MlpRequest).parameters["packed"].default is False
-    assert sparse_field.MlpRequest().packed is False and sparse_field.MlpRequest(packed=True).packed is True
+    Req = sparse_field.FieldRequest
+    assert inspect.signature(Req).parameters["packed"].default is False
+    assert Req(bf16=True).packed is False and Req(bf16=True, packed=True).packed is True
     assert list(inspect.signature(sparse_field.check_feature_precision).parameters) == ["value", "mlp_bf16", "prefix"]
     assert "feature_precision" not in inspect.signature(nerf.OccupancyGrid.update).parameters
 

@@ -78,35 +78,41 @@ def test_render_rays_and_render_refuse_before_anything_else():
 
 
 def test_request_carries_the_flag():
-    """The request of mlp_precision="bf16" carries it: no fourth attribute on the points, no global switch."""
-    from indoor_nerf_amd.render import _query, _query_mlp
+    """The one request carries it: one attribute on the points for every combination, no global switch."""
+    from indoor_nerf_amd.render import _query
+    Req = sparse_field.FieldRequest
     pts, seen = torch.zeros(2, 3, 3), []
 
     def foreign(p, viewdirs, fn):
         seen.append({k: v for k, v in vars(p).items() if k.startswith("_nerf")})
         return torch.zeros(2, 3, 4)
 
-    assert refusal(_query_mlp, foreign, pts, None, None, True, False, True) == FOREIGN
-    assert list(seen[-1]) == ["_nerf_mlp"] and seen[-1]["_nerf_mlp"].packed is True
-    assert refusal(_query_mlp, foreign, pts, None, None, True) == FOREIGN
-    assert seen[-1]["_nerf_mlp"].packed is False
-    assert refusal(_query, foreign, pts, None, None, None, None, True, True, True) == \
+    assert refusal(_query, foreign, pts, None, None, Req(bf16=True, packed=True)) == FOREIGN
+    assert list(seen[-1]) == ["_nerf_req"] and seen[-1]["_nerf_req"].packed is True
+    assert refusal(_query, foreign, pts, None, None, Req(bf16=True)) == FOREIGN
+    assert list(seen[-1]) == ["_nerf_req"] and seen[-1]["_nerf_req"].packed is False
+    assert refusal(_query, foreign, pts, None, None, Req(bf16=True, half=True, packed=True)) == \
         "render_rays: table_precision needs a network_query_fn that calls this package's run_network"
-    assert sorted(seen[-1]) == ["_nerf_mlp", "_nerf_tab"] and seen[-1]["_nerf_mlp"].packed is True
+    assert list(seen[-1]) == ["_nerf_req"] and seen[-1]["_nerf_req"].packed is True
+    for kw in (dict(grid=object()), dict(early=(None, None, 1e-3, 8)), dict(half=True), dict(grid=object(), bf16=True),
+               dict(march=sparse_field.MarchList(torch.zeros(2, 16)), bf16=True, half=True, packed=True)):
+        refusal(_query, foreign, pts, None, None, Req(**kw))
+        assert list(seen[-1]) == ["_nerf_req"], kw
     assert not any(k.startswith("_nerf") for k in vars(pts))
-    assert inspect.signature(_query).parameters["packed"].default is False
+    assert inspect.signature(Req).parameters["packed"].default is False
     assert sparse_field.is_packed(None) is False
-    assert sparse_field.is_packed(sparse_field.MlpRequest()) is False
-    assert sparse_field.is_packed(sparse_field.MlpRequest(packed=True)) is True
+    assert sparse_field.is_packed(Req(bf16=True)) is False
+    assert sparse_field.is_packed(Req(bf16=True, packed=True)) is True
 
 
 def test_feature_buffer_halves_the_bytes():
+    Req = sparse_field.FieldRequest
     for n in (0, 1, 48):
         buf, w, dt = sparse_field.feature_buffer(None, n, "cpu")
         assert (buf.numel(), w, dt, buf.dtype) == (2 * n, 2, torch.float32, torch.float32)
-        buf, w, dt = sparse_field.feature_buffer(sparse_field.MlpRequest(), n, "cpu")
+        buf, w, dt = sparse_field.feature_buffer(Req(bf16=True), n, "cpu")
         assert (buf.numel(), w, dt) == (2 * n, 2, torch.float32)
-        pk, w, dt = sparse_field.feature_buffer(sparse_field.MlpRequest(packed=True), n, "cpu")
+        pk, w, dt = sparse_field.feature_buffer(Req(bf16=True, packed=True), n, "cpu")
         assert (pk.numel(), w, dt, pk.dtype) == (n, 1, torch.int32, torch.int32)
         assert 2 * pk.numel() * pk.element_size() == buf.numel() * buf.element_size()
 

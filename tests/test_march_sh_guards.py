@@ -72,30 +72,35 @@ def test_render_rays_and_render_refuse_before_anything_else():
 
 
 def test_request_carries_either_the_rows_or_the_index():
-    """No global switch and no further attribute on the points: the MarchRequest holds sh_c, or ray_c and sh_rec."""
-    Req = sparse_field.MarchRequest
+    """No global switch and no further attribute on the points: the request's MarchList holds sh_c, or ray_c and
+    sh_rec (`used` is the request's)."""
+    Req = sparse_field.MarchList
     sh_c, ray_c, rec = torch.zeros(5, 16), torch.zeros(5, dtype=torch.int32), torch.zeros(2, 40)
     a = Req(sh_c, 1000)
-    assert a.sh_c is sh_c and a.ray_c is None and a.sh_rec is None and a.max_points == 1000 and a.used is False
+    assert a.sh_c is sh_c and a.ray_c is None and a.sh_rec is None and a.max_points == 1000
+    assert sparse_field.FieldRequest(march=a).used is False
     b = Req(None, 1000, ray_c=ray_c, sh_rec=rec)
-    assert b.sh_c is None and b.ray_c is ray_c and b.sh_rec is rec and b.what == "march"
+    assert b.sh_c is None and b.ray_c is ray_c and b.sh_rec is rec and sparse_field.FieldRequest(march=b).what == "march"
     for args, kw in (((None,), {}), ((sh_c,), dict(ray_c=ray_c, sh_rec=rec)), ((None,), dict(ray_c=ray_c)),
                      ((None,), dict(sh_rec=rec)), ((sh_c,), dict(sh_rec=rec))):
         assert refusal(Req, *args, **kw) == "march: a request carries either sh_c or (ray_c, sh_rec)"
-    assert sorted(k for k in vars(b)) == ["max_points", "ray_c", "sh_c", "sh_rec", "used"]
+    assert sorted(k for k in vars(b)) == ["max_points", "ray_c", "sh_c", "sh_rec"]
 
 
 def test_mlp_forward_chooses_the_entry(monkeypatch):
-    """sparse_field.mlp_forward is the one place that picks the entry: by the MlpRequest, and by whether the call
-    brings a ray index."""
+    """sparse_field.mlp_forward is the one place that picks the entry: by the request's bf16 and packed (not by there
+    being a request: one with only half=True runs the fp32-accurate entries), and by whether the call brings a ray
+    index."""
     import indoor_nerf_amd._lib as L
     seen = []
     monkeypatch.setattr(L, "call", lambda name, *args: seen.append((name, args)))
     monkeypatch.setattr(L, "stream", lambda: "stream")
-    Mlp = sparse_field.MlpRequest
+    Req = sparse_field.FieldRequest
     for mlp, rows_entry, rays_entry, stride in ((None, "nerf_mlp_fwd_ord", "nerf_mlp_fwd_rays", 2),
-                                                (Mlp(), "nerf_mlp_fwd_bf16", "nerf_mlp_fwd_bf16_rays", 2),
-                                                (Mlp(packed=True), "nerf_mlp_fwd_bf16_pkbf", "nerf_mlp_fwd_bf16_pkbf_rays", 1)):
+                                                (Req(bf16=True), "nerf_mlp_fwd_bf16", "nerf_mlp_fwd_bf16_rays", 2),
+                                                (Req(bf16=True, packed=True), "nerf_mlp_fwd_bf16_pkbf",
+                                                 "nerf_mlp_fwd_bf16_pkbf_rays", 1),
+                                                (Req(half=True), "nerf_mlp_fwd_ord", "nerf_mlp_fwd_rays", 2)):
         sparse_field.mlp_forward(mlp, "feat", 77, "sh_c", "keep", 9, "w", "raw", None)
         assert seen[-1][0] == rows_entry and seen[-1][1][:7] == ("feat", stride, 77, "sh_c", 16, None, 1)
         sparse_field.mlp_forward(mlp, "feat", 77, None, "keep", 9, "w", "raw", None, ("ray_of", "rec", 4))

@@ -99,7 +99,7 @@ def test_run_network_refuses_before_the_eager_path():
     import indoor_nerf_amd as nerf
     emb, net, _, sh = field_modules()
     pts = torch.zeros(2, 3, 3)
-    req = pts._nerf_mlp = sparse_field.MlpRequest()
+    req = pts._nerf_req = sparse_field.FieldRequest(bf16=True)
     assert req.used is False
     with torch.no_grad():
         assert refusal(nerf.run_network, pts, None, net, emb, sh) == \
@@ -110,16 +110,19 @@ def test_run_network_refuses_before_the_eager_path():
 def test_foreign_query_function_raises():
     """A query function that does not reach this package's run_network leaves the request unused: render_rays'
     field call raises instead of returning an fp32 render."""
-    from indoor_nerf_amd.render import _query, _query_mlp
+    from indoor_nerf_amd.render import _query
     pts, seen = torch.zeros(2, 3, 3), []
 
     def foreign(p, viewdirs, fn):
-        seen.append(getattr(p, "_nerf_mlp", None))
+        seen.append(getattr(p, "_nerf_req", None))
         return torch.zeros(2, 3, 4)
 
     words = "render_rays: mlp_precision needs a network_query_fn that calls this package's run_network"
-    assert refusal(_query_mlp, foreign, pts, None, None, True) == words
-    assert isinstance(seen[0], sparse_field.MlpRequest) and not hasattr(pts, "_nerf_mlp")
-    assert refusal(_query, foreign, pts, None, None, None, None, True) == words
+    req = sparse_field.FieldRequest(bf16=True)
+    assert refusal(_query, foreign, pts, None, None, req) == words
+    assert seen[0] is req and req.bf16 is True and not hasattr(pts, "_nerf_req")
+    assert refusal(_query, foreign, pts, None, None, req=sparse_field.FieldRequest(bf16=True)) == words
     # without the keyword the same function is simply called, with nothing attached
-    assert _query_mlp(foreign, pts, None, None, False).shape == (2, 3, 4) and seen[-1] is None
+    raw, stops = _query(foreign, pts, None, None, None)
+    assert raw.shape == (2, 3, 4) and stops is None and seen[-1] is None
+    assert _query(foreign, pts, None, None)[0].shape == (2, 3, 4) and seen[-1] is None

@@ -115,8 +115,8 @@ def test_run_network_refuses_before_the_eager_path():
     import indoor_nerf_amd as nerf
     emb, net, _, sh = field_modules()
     pts = torch.zeros(2, 3, 3)
-    req = pts._nerf_tab = sparse_field.TableRequest()
-    assert req.used is False and req.what == "table_precision"
+    req = pts._nerf_req = sparse_field.FieldRequest(half=True)
+    assert req.used is False and req.blame == "table_precision"
     with torch.no_grad():
         assert refusal(nerf.run_network, pts, None, net, emb, sh) == \
             "table_precision: needs the fused field call (SHEncoder view encoding, viewdirs, inputs [R, S, 3])"
@@ -125,26 +125,28 @@ def test_run_network_refuses_before_the_eager_path():
 
 def test_foreign_query_function_raises():
     """A query function that does not reach this package's run_network leaves the request unused: render_rays'
-    field call raises instead of rendering from the fp32 tables. With mlp_precision="bf16" beside it both requests
-    ride on the points, and the table request is the one checked first (it is the inner one)."""
-    from indoor_nerf_amd.render import _query, _query_mlp, _query_tab
+    field call raises instead of rendering from the fp32 tables. With mlp_precision="bf16" beside it the one request
+    carries both, and table_precision is the keyword blamed (FieldRequest.blame: tables before the MLP)."""
+    from indoor_nerf_amd.render import _query
+    Req = sparse_field.FieldRequest
     pts, seen = torch.zeros(2, 3, 3), []
 
     def foreign(p, viewdirs, fn):
-        seen.append((getattr(p, "_nerf_tab", None), getattr(p, "_nerf_mlp", None)))
+        seen.append(getattr(p, "_nerf_req", None))
         return torch.zeros(2, 3, 4)
 
-    assert refusal(_query_tab, foreign, pts, None, None, True) == FOREIGN
-    assert isinstance(seen[-1][0], sparse_field.TableRequest) and seen[-1][1] is None
-    assert not hasattr(pts, "_nerf_tab")
-    assert refusal(_query_mlp, foreign, pts, None, None, False, True) == FOREIGN
-    assert refusal(_query_mlp, foreign, pts, None, None, True, True) == FOREIGN
-    assert isinstance(seen[-1][0], sparse_field.TableRequest) and isinstance(seen[-1][1], sparse_field.MlpRequest)
-    assert refusal(_query, foreign, pts, None, None, None, None, False, True) == FOREIGN
-    assert refusal(_query, foreign, pts, None, None, None, None, half=True) == FOREIGN
+    assert refusal(_query, foreign, pts, None, None, Req(half=True)) == FOREIGN
+    assert isinstance(seen[-1], Req) and seen[-1].half is True and seen[-1].bf16 is False
+    assert not hasattr(pts, "_nerf_req")
+    assert refusal(_query, foreign, pts, None, None, Req(half=True, bf16=False)) == FOREIGN
+    assert refusal(_query, foreign, pts, None, None, Req(half=True, bf16=True)) == FOREIGN
+    assert seen[-1].half is True and seen[-1].bf16 is True
+    assert refusal(_query, foreign, pts, None, None, Req(grid=object(), half=True)) == FOREIGN
+    assert refusal(_query, foreign, pts, None, None, req=Req(half=True)) == FOREIGN
     # without the keyword the same function is simply called, with nothing attached
-    assert _query_tab(foreign, pts, None, None, False).shape == (2, 3, 4) and seen[-1] == (None, None)
-    assert _query_mlp(foreign, pts, None, None, False).shape == (2, 3, 4) and seen[-1] == (None, None)
+    assert _query(foreign, pts, None, None, None)[0].shape == (2, 3, 4) and seen[-1] is None
+    assert _query(foreign, pts, None, None)[0].shape == (2, 3, 4) and seen[-1] is None
     # mlp_precision's own message is unchanged
-    assert refusal(_query_mlp, foreign, pts, None, None, True) == \
+    assert Req(half=True, bf16=True).blame == "table_precision" and Req(bf16=True).blame == "mlp_precision"
+    assert refusal(_query, foreign, pts, None, None, Req(bf16=True)) == \
         "render_rays: mlp_precision needs a network_query_fn that calls this package's run_network"
