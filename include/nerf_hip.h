@@ -1051,6 +1051,15 @@ int nerf_mlp_fwd_bf16_pkbf_rays(const uint32_t* d_featw, int64_t feat_stride_poi
                                 const uint8_t* d_keep, int64_t n_points,
                                 const nerf_mlp_weights* weights, float* d_raw, void* stream);
 
+/* Debug: the bf16 weight image that every block of the fp32-accurate MLP kernels builds in its prologue
+ * (csrc/field_x6.hip), copied out by one block that runs that prologue. d_out receives 3 x 11,136 bf16
+ * elements (66,816 B): piece k (k = 0, 1, 2; v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1), round to
+ * nearest even) at element 11,136 k, and inside a piece the row-major matrices W0 [64][32] at element 0, W1
+ * [16][64] at 2,304, C0' [64][32] at 3,392, C1 [64][64] at 5,696 and C2 [16][64] at 10,048, rows of 32 columns 36
+ * elements apart and rows of 64 columns 68. C0' row r: column 0 is 0, columns 1..15 are c0[r][16..30], columns
+ * 16..31 are c0[r][0..15]; C2 rows 3..15 are 0. The 4 pad elements behind each row are unspecified. */
+int nerf_mlp_weight_image(const nerf_mlp_weights* weights, void* d_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

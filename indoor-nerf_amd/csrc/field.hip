@@ -26,6 +26,7 @@ int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream);
 int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_t stream);
 int launch_mlp_fwd_x6_rays(const MlpArgs& a, const int32_t* ray_ix, hipStream_t stream);
 int launch_mlp_fwd_bf16_rays(const MlpArgs& a, bool packed, const int32_t* ray_ix, hipStream_t stream);
+int launch_mlp_weight_image(const nerf_mlp_weights& W, void* d_out, hipStream_t stream);
 
 static int fill_args(MlpArgs& a, const float* d_feat, int64_t sp, int64_t sl, const float* d_sh, int64_t sh_stride,
                      const float* d_viewdirs, int64_t spr, const uint8_t* d_keep, int64_t n,
@@ -68,6 +69,12 @@ extern "C" int nerf_sh4_fwd(const float* d_dirs, int64_t n, float* d_out, void* 
     hipLaunchKernelGGL(sh4_fwd_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, as_stream(stream), d_dirs, n, d_out);
     NERF_CHECK_LAUNCH("sh4_fwd");
     return NERF_OK;
+}
+
+extern "C" int nerf_mlp_weight_image(const nerf_mlp_weights* weights, void* d_out, void* stream) {
+    NERF_REQUIRE(weights && weights->w0 && weights->w1 && weights->c0 && weights->c1 && weights->c2 && d_out,
+                 "mlp_weight_image: null pointer");
+    return launch_mlp_weight_image(*weights, d_out, as_stream(stream));
 }
 
 extern "C" size_t nerf_mlp_h3_bytes(int64_t n_points) {

@@ -108,6 +108,36 @@ __device__ __forceinline__ floatx16 mma6(const S3& A, const S3& B, floatx16 c) {
     return c;
 }
 
+// ---- prologue share (diagnostic build only, -DNERF_X6_PROLOGUE_PROF, tools/prologue_prof.py) -------
+// Per block of mlp_fwd_x6_kernel (kernel 0) and mlp_bwd_x6cg_kernel (kernel 1): s_memtime at kernel
+// entry [0], behind the weight-image prologue's barrier [1] and at the end of the block's last wave [2],
+// and the 100 MHz real time at entry [3] and end [4] (the cycle length of the first three).
+// The stamps are calls (noinline): inlined, they push the forward's register allocation from 109 to 138 VGPRs, one
+// block per CU instead of two, and the block lifetimes measured are then another kernel's.
+#ifdef NERF_X6_PROLOGUE_PROF
+constexpr int kProProfBlocks = 512;
+__device__ unsigned long long pro_prof[2 * kProProfBlocks * 5];
+__device__ __noinline__ void pro_stamp(int kernel, int slot) {
+    if (threadIdx.x == 0 && blockIdx.x < kProProfBlocks) {
+        unsigned long long* r = pro_prof + (kernel * kProProfBlocks + blockIdx.x) * 5;
+        r[slot] = __builtin_amdgcn_s_memtime();
+        if (slot == 0) r[3] = __builtin_amdgcn_s_memrealtime();
+    }
+}
+__device__ __noinline__ void pro_end(int kernel) {
+    if ((threadIdx.x & 63) == 0 && blockIdx.x < kProProfBlocks) {
+        unsigned long long* r = pro_prof + (kernel * kProProfBlocks + blockIdx.x) * 5;
+        atomicMax(r + 2, (unsigned long long)__builtin_amdgcn_s_memtime());
+        atomicMax(r + 4, (unsigned long long)__builtin_amdgcn_s_memrealtime());
+    }
+}
+#define PRO_STAMP(kernel, slot) pro_stamp(kernel, slot)
+#define PRO_END(kernel) pro_end(kernel)
+#else
+#define PRO_STAMP(kernel, slot)
+#define PRO_END(kernel)
+#endif
+
 // ---- LDS images (bf16 elements) ----------------------------------------------------------------
 constexpr int S64 = 68, S32 = 36;            // padded row strides of 64- and 32-column matrices
 constexpr int IM_W0 = 0;                     // [64][S32]
@@ -117,55 +147,98 @@ constexpr int IM_C1 = IM_C0 + 64 * S32;      // [64][S64]
 constexpr int IM_C2 = IM_C1 + 64 * S64;      // [16][S64]
 constexpr int IM_PIECE = IM_C2 + 16 * S64;   // 11,136 elements per piece
 constexpr int IM_BYTES = 3 * IM_PIECE * 2;   // 66,816 B
-// logical (unpadded) element index ranges of the five matrices, for the fill loop
-constexpr int L_W1 = 2048, L_C0 = 3072, L_C1 = 5120, L_C2 = 9216, L_END = 10240;
 // backward staging of one 32-row gradient tile [32 points][32], three bf16 pieces
 constexpr int STG_PIECE = 32 * S32;
 
-__device__ __forceinline__ float image_value(int idx, const nerf_mlp_weights& W) {
-    if (idx < L_W1) return W.w0[idx];                                     // [64][32]
-    if (idx < L_C0) return W.w1[idx - L_W1];                              // [16][64]
-    if (idx < L_C1) {
-        const int k = idx - L_C0, r = k >> 5, c = k & 31;
-        if (c == 0) return 0.f;                                           // sigma slot
-        return c < 16 ? W.c0[r * 31 + 15 + c] : W.c0[r * 31 + c - 16];    // geo 1..15 | SH 0..15
-    }
-    if (idx < L_C2) return W.c1[idx - L_C1];
-    const int k = idx - L_C2;
-    return (k >> 6) < 3 ? W.c2[k] : 0.f;
+// ---- the weight-image prologue -------------------------------------------------------------------
+// Every block builds the image from the fp32 weights in ONE round of loads. A thread's unit of work is
+// four consecutive columns of one row: one 16-B load, two split2 (the tile loop's own split), one
+// ds_write_b64 per piece (rows are 72 / 136 B apart, so a group of four columns is 8-B aligned). The
+// 2,560 units of the five matrices fall on the 512 threads of a block by class, each class with its
+// own compile-time decode:
+//   W0  [64][32]  512 units, one per thread          C1 [64][64] 1,024 units, two per thread
+//   C0' [64][32]  512 units, one per thread: the columns 4g..4g+3 of row r are c0[31r + s .. + 3] with
+//                 s = 15 + 4g (g < 4, geo; column 0, the sigma slot, is 0) or 4g - 16 (SH); rows of 31
+//                 floats are not 16-B aligned, so four 4-B loads (the last one ends at c0[64 * 31 - 1])
+//   W1  [16][64]  256 units on threads 0..255        C2 [16][64] 256 units on threads 256..511, the
+//                 13 x 16 units of rows 3..15 zeros without a load
+// and the fp32 images of C2 (AUX_C2F: the forward's output layer, AUX_C2B: the backward's ga3, with its
+// zero block of transposed operands) read c2 in the same round. All loads are issued before the first
+// split. The image is, in every bit, the one an element-at-a-time loop with (__bf16) conversions
+// wrote (tests/test_gpu_mlp_prologue.py); the row pads stay unwritten.
+// NP: the pieces kept (3; 1: the bf16 forward's image, piece 0). A16: w0, w1, c1 and c2 are 16-B aligned
+// (tensors of their own always are); otherwise a unit's four values are loaded one by one. The threads
+// 0..kFillThreads-1 of a block call it (the 1,024-thread forward: its first 8 waves).
+enum { AUX_NONE, AUX_C2F, AUX_C2B };
+constexpr int C2F_FLOATS = 2 * 3 * 32;   // rgb_c2's image [h][o][32]
+constexpr int C2B_FLOATS = 2 * 64 * 2;   // ga3_f32's image [t][lane][m]
+constexpr int kFillThreads = 512;        // the threads that build the image
+
+template <bool A16>
+__device__ __forceinline__ float4 fill_load4(const float* p) {
+    if constexpr (A16) return *reinterpret_cast<const float4*>(p);
+    else return make_float4(p[0], p[1], p[2], p[3]);
 }
 
-// Every block's prologue. The loads of a round (kFillRound per thread) are issued before the first
-// split / store: one memory round trip per round instead of one per element (a thread of a 512-wide
-// block has 20 elements; one at a time, their L2 latencies were serial).
-constexpr int kFillRound = 10;
-__device__ inline void fill_images(__bf16* img, const nerf_mlp_weights& W) {
-    for (int base = threadIdx.x; base < L_END; base += kFillRound * blockDim.x) {
-        float v[kFillRound];
-#pragma unroll
-        for (int u = 0; u < kFillRound; ++u) {
-            const int idx = base + u * (int)blockDim.x;
-            v[u] = idx < L_END ? image_value(idx, W) : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < kFillRound; ++u) {
-            const int idx = base + u * (int)blockDim.x;
-            if (idx >= L_END) continue;
-            int off;
-            if (idx < L_W1) off = IM_W0 + (idx >> 5) * S32 + (idx & 31);
-            else if (idx < L_C0) { const int k = idx - L_W1; off = IM_W1 + (k >> 6) * S64 + (k & 63); }
-            else if (idx < L_C1) { const int k = idx - L_C0; off = IM_C0 + (k >> 5) * S32 + (k & 31); }
-            else if (idx < L_C2) { const int k = idx - L_C1; off = IM_C1 + (k >> 6) * S64 + (k & 63); }
-            else { const int k = idx - L_C2; off = IM_C2 + (k >> 6) * S64 + (k & 63); }
-            const __bf16 a0 = (__bf16)v[u];
-            const float r1 = v[u] - (float)a0;
-            const __bf16 a1 = (__bf16)r1;
-            const __bf16 a2 = (__bf16)(r1 - (float)a1);
-            img[off] = a0;
-            img[IM_PIECE + off] = a1;
-            img[2 * IM_PIECE + off] = a2;
-        }
+template <int NP>
+__device__ __forceinline__ void fill_store4(__bf16* img, int off, const float4& v) {
+    uint32_t lo[3], hi[3];
+    if constexpr (NP == 3) {
+        split2(v.x, v.y, lo[0], lo[1], lo[2]);
+        split2(v.z, v.w, hi[0], hi[1], hi[2]);
+    } else {
+        lo[0] = pk_bf16(v.x, v.y);
+        hi[0] = pk_bf16(v.z, v.w);
     }
+#pragma unroll
+    for (int p = 0; p < NP; ++p) *reinterpret_cast<u32x2*>(img + p * IM_PIECE + off) = u32x2{lo[p], hi[p]};
+}
+
+template <int NP, int AUX, bool A16>
+__device__ __forceinline__ void fill_round(__bf16* img, float* aux, const nerf_mlp_weights& W) {
+    const int t = threadIdx.x;
+    const int r8 = t >> 3, g8 = t & 7;                      // a row of 32 columns: 8 units
+    const int r16 = t >> 4, g16 = t & 15;                   // a row of 64 columns: 16 units
+    const int u = t & 255, ru = u >> 4;
+    const bool is_c2 = t >= 256, live = !is_c2 || ru < 3;   // W1 | C2, rows 3..15 of C2: zeros
+    // the round's loads
+    const float4 v_w0 = fill_load4<A16>(W.w0 + 4 * t);
+    float4 v_u = fill_load4<A16>((is_c2 ? W.c2 : W.w1) + (live ? 4 * u : 0));
+    const float4 v_c1a = fill_load4<A16>(W.c1 + 4 * t), v_c1b = fill_load4<A16>(W.c1 + 4 * (t + kFillThreads));
+    const float* s0 = W.c0 + 31 * r8 + (g8 < 4 ? 15 + 4 * g8 : 4 * g8 - 16);
+    float4 v_c0 = make_float4(s0[0], s0[1], s0[2], s0[3]);
+    float x = 0.f;
+    if constexpr (AUX == AUX_C2F) {   // c2f[t] = C2[o][32 (k >> 4) + row_of(k & 15, h)], t = 96 h + 32 o + k
+        const int i = t < C2F_FLOATS ? t : 0, hh = i / 96, o = (i / 32) % 3, k = i & 31;
+        x = W.c2[o * 64 + 32 * (k >> 4) + row_of(k & 15, hh)];
+    }
+    if constexpr (AUX == AUX_C2B) {   // c2b[t] = C2[2m + (ln >> 5)][32 tt + (ln & 31)] (0 past row 2), t = 128 tt + 2 ln + m
+        const int tt = u >> 7, ln = (u >> 1) & 63, k = 2 * (u & 1) + (ln >> 5);
+        const bool in = t < C2B_FLOATS && k < 3;
+        x = W.c2[in ? k * 64 + 32 * tt + (ln & 31) : 0];
+        if (!in) x = 0.f;
+    }
+    if (!live) v_u = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (g8 == 0) v_c0.x = 0.f;                              // the sigma slot
+    fill_store4<NP>(img, IM_W0 + r8 * S32 + 4 * g8, v_w0);
+    fill_store4<NP>(img, (is_c2 ? IM_C2 : IM_W1) + ru * S64 + 4 * (u & 15), v_u);
+    fill_store4<NP>(img, IM_C0 + r8 * S32 + 4 * g8, v_c0);
+    fill_store4<NP>(img, IM_C1 + r16 * S64 + 4 * g16, v_c1a);
+    fill_store4<NP>(img, IM_C1 + (r16 + 32) * S64 + 4 * g16, v_c1b);
+    if constexpr (AUX == AUX_C2F) {
+        if (t < C2F_FLOATS) aux[t] = x;
+    }
+    if constexpr (AUX == AUX_C2B) {
+        if (t < C2B_FLOATS) aux[t] = x;
+    }
+}
+
+// threads 0..kFillThreads-1; aux: c2f (AUX_C2F) or c2b (AUX_C2B)
+template <int NP, int AUX>
+__device__ __forceinline__ void fill_images(__bf16* img, float* aux, const nerf_mlp_weights& W) {
+    const uintptr_t bits = (uintptr_t)W.w0 | (uintptr_t)W.w1 | (uintptr_t)W.c1 | (uintptr_t)W.c2;
+    if ((bits & 15) == 0) fill_round<NP, AUX, true>(img, aux, W);
+    else fill_round<NP, AUX, false>(img, aux, W);
 }
 
 // A operand of Y = M X for the output row r of lane m: elements i <-> columns
@@ -536,14 +609,7 @@ __device__ __forceinline__ void fwd_chain(const __bf16* img, const InX6& in, Act
 // 32t + row_of(r, h): it forms the three partial dot products over those 32 neurons (fp32 FMA chains,
 // weights from an fp32 LDS image [h][o][32]: ds_read_b128 broadcasts), and two v_permlane32_swap
 // exchanges add the lane halves' partials. Every lane ends with all three outputs of its point.
-constexpr int C2F_FLOATS = 2 * 3 * 32;
-
-__device__ inline void fill_c2f(float* c2f, const nerf_mlp_weights& W) {
-    for (int idx = threadIdx.x; idx < C2F_FLOATS; idx += blockDim.x) {
-        const int hh = idx / 96, o = (idx / 32) % 3, k = idx & 31;
-        c2f[idx] = W.c2[o * 64 + 32 * (k >> 4) + row_of(k & 15, hh)];
-    }
-}
+// (The image c2f is built by the prologue, fill_images<.., AUX_C2F>.)
 
 __device__ __forceinline__ float swap_half_sum(float lo, float hi, float& other) {
     // lanes 32..63 of `lo` trade places with lanes 0..31 of `hi`: afterwards lanes 0..31 hold
@@ -589,14 +655,7 @@ __device__ __forceinline__ void rgb_c2(const float* c2f, const floatx16 (&h3)[2]
 #ifndef NERF_X6_GA3_F32
 #define NERF_X6_GA3_F32 1
 #endif
-constexpr int C2B_FLOATS = 2 * 64 * 2;
-
-__device__ inline void fill_c2b(float* c2b, const nerf_mlp_weights& W) {
-    for (int idx = threadIdx.x; idx < C2B_FLOATS; idx += blockDim.x) {
-        const int t = idx >> 7, ln = (idx >> 1) & 63, m = idx & 1, k = 2 * m + (ln >> 5);
-        c2b[idx] = k < 3 ? W.c2[k * 64 + 32 * t + (ln & 31)] : 0.f;
-    }
-}
+// (The image c2b is built by the prologue, fill_images<.., AUX_C2B>.)
 
 __device__ __forceinline__ floatx16 ga3_f32(const float* c2b, int t, float b0, float b1, int lane) {
     const float2 a = *reinterpret_cast<const float2*>(c2b + 2 * (64 * t + lane));
@@ -617,22 +676,28 @@ __device__ __forceinline__ uint32_t h3_off(int64_t tile, int t, int q, int lane)
 // RayIx: empty (the kernel as it was: the same parameter list, the same instructions), or one const int32_t*, the
 // ray index of nerf_mlp_fwd_rays, which selects the loaders that read the SH records through it
 template <bool QUANT, typename... RayIx>
-// 512-thread blocks: the 66.8 KB weight image is shared by 8 waves, so two blocks per CU give 4
-// waves per SIMD (105 VGPRs) instead of 2 with 256-thread blocks
-__global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a, RayIx... ray_ix) {
+// ONE 1,024-thread block per CU: the 66.8 KB weight image is shared by 16 waves, 4 per SIMD (110 VGPRs), and is
+// built once per CU, by the block's first 8 waves. (Two 512-thread blocks per CU, the same 4 waves per SIMD, each
+// built a copy of its own: step 1.159 -> 1.141 ms, DESIGN.md §4. The image's units spread over all 1,024 threads
+// by wave-uniform branches: 128 VGPRs and 56 B of scratch, not pursued.)
+__global__ void __launch_bounds__(1024, 1) mlp_fwd_x6_kernel(MlpArgs a, RayIx... ray_ix) {
     __shared__ __attribute__((aligned(16))) __bf16 img[3 * IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
-    fill_images(img, a.W);
-    fill_c2f(c2f, a.W);
-    __syncthreads();
+    PRO_STAMP(0, 0);
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
-    QuantRec aq{};
-    if constexpr (QUANT) aq = *a.aq;
     const int64_t n_tiles = (a.P + 31) / 32;
     const int wpb = blockDim.x >> 6;
-    for (int64_t tile = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6); tile < n_tiles; tile += (int64_t)gridDim.x * wpb) {
-        InX6 in;
-        load_in_x6(a, tile, j, h, in, ray_ix...);
+    const int64_t tile0 = (int64_t)blockIdx.x * wpb + (threadIdx.x >> 6);
+    // the wave's first tile's inputs are in flight under the prologue (a wave with no tile loads nothing);
+    // the loop loads a tile's inputs at the end of the tile before it, so its body is the tile as it was
+    InX6 in;
+    if (tile0 < n_tiles) load_in_x6(a, tile0, j, h, in, ray_ix...);
+    if (threadIdx.x < kFillThreads) fill_images<3, AUX_C2F>(img, c2f, a.W);   // the first 8 waves build it
+    __syncthreads();
+    PRO_STAMP(0, 1);
+    QuantRec aq{};
+    if constexpr (QUANT) aq = *a.aq;
+    for (int64_t tile = tile0; tile < n_tiles;) {
         ActX6 f;
         const int z = opaque_zero();
         fwd_chain<QUANT>(img + z, in, f, lane, aq);
@@ -658,7 +723,10 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a, RayIx... 
 #pragma unroll
             for (int r = 0; r < 8; ++r) a.geo_out[16u * orow + row_of(r, h)] = f.o[r];
         }
+        tile += (int64_t)gridDim.x * wpb;
+        if (tile < n_tiles) load_in_x6(a, tile, j, h, in, ray_ix...);
     }
+    PRO_END(0);
 }
 
 // Calibration-only launch of the activation quantizer (quantization.py:97-119 on the first
@@ -666,7 +734,7 @@ __global__ void __launch_bounds__(512, 2) mlp_fwd_x6_kernel(MlpArgs a, RayIx... 
 // atomic pair per wave (order-preserving u32 images of the floats).
 __global__ void __launch_bounds__(512, 2) mlp_act_minmax_x6_kernel(MlpArgs a) {
     __shared__ __attribute__((aligned(16))) __bf16 img[3 * IM_PIECE];
-    fill_images(img, a.W);
+    fill_images<3, AUX_NONE>(img, nullptr, a.W);
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     const int64_t n = a.calib_points < a.P ? a.calib_points : a.P;
@@ -772,7 +840,7 @@ __device__ __forceinline__ void stage_arrF(float* actF, const float* v, int row0
 template <bool QUANT, bool SAVED>
 __device__ __forceinline__ void bwd_chain_role(const MlpArgs& a, const __bf16* img, __bf16* stA, __bf16* stG,
                                                int* ready, int* ack, int p, int lane, const QuantRec& aq, int blk,
-                                               int nblk, const float* c2b) {
+                                               int nblk, const float* c2b, const InX6& in_first) {
     const int j = lane & 31, h = lane >> 5;
     float* actF = reinterpret_cast<float*>(stA);
     int seq = 0;
@@ -796,12 +864,15 @@ __device__ __forceinline__ void bwd_chain_role(const MlpArgs& a, const __bf16* i
     __bf16* const stGb[2] = {stG, stG + 3 * STG_PIECE};
     auto publish = [&]() { flag_set(ready, ++seq); };
     const int64_t n_pts = bwd_points(a);
-    const int64_t n_tiles = (n_pts + 31) / 32;
+    // (wave-uniform and below 2^26, fits_u32: kept in a scalar register, not in two vector registers)
+    const int64_t n_tiles = __builtin_amdgcn_readfirstlane((int)((n_pts + 31) / 32));
 #if NERF_X6_BWD_PREFETCH
     // the next tile's inputs are loaded after stage 5 (the forward state is dead by then) and are in
-    // flight during stages 6 and 7 instead of stalling the next tile's forward recompute
-    InX6 in_next;
-    if ((int64_t)blk * 4 + p < n_tiles) load_in_x6_bwd(a, n_pts, (int64_t)blk * 4 + p, j, h, in_next);
+    // flight during stages 6 and 7 instead of stalling the next tile's forward recompute; the first
+    // tile's were loaded by the kernel before the weight-image prologue
+    InX6 in_next = in_first;
+#else
+    (void)in_first;
 #endif
     for (int64_t tile = (int64_t)blk * 4 + p; tile < n_tiles; tile += (int64_t)nblk * 4) {
         const __bf16* imt = img + opaque_zero();
@@ -1101,7 +1172,7 @@ __device__ __forceinline__ void bwd_wgrad_role(const MlpArgs& a, const __bf16* i
     auto take = [&]() { flag_wait(ready, seq + 1, &waited); };
     auto release = [&]() { flag_set_now(ack, ++seq); };
     const int64_t n_pts = bwd_points(a);
-    const int64_t n_tiles = (n_pts + 31) / 32;
+    const int64_t n_tiles = __builtin_amdgcn_readfirstlane((int)((n_pts + 31) / 32));   // as the chain role's
     for (int64_t tile = (int64_t)blk * 4 + p; tile < n_tiles; tile += (int64_t)nblk * 4) {
         {   // 1: dC2
             Ops16 o;
@@ -1239,20 +1310,29 @@ __global__ void __launch_bounds__(512, 1) mlp_bwd_x6cg_kernel(MlpBwdJobs jobs) {
     const bool wgrad_wave = wv >= 4;
     __bf16* stA = lds + 3 * IM_PIECE + p * ST_CG;   // fp32 activation image (actF)
     __bf16* stG = stA + 2 * ACTF_FLOATS;
-    fill_images(img, a.W);
-    fill_c2b(c2b, a.W);
-    for (int i = threadIdx.x; i < X6_ZBLK_ELEMS / 2; i += blockDim.x) reinterpret_cast<uint32_t*>(img + X6_ZBLK)[i] = 0u;
+    PRO_STAMP(1, 0);
+    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
+    InX6 in_first;
+#if NERF_X6_BWD_PREFETCH
+    // a chain wave's first tile's inputs (bwd_chain_role's in_next) are in flight under the prologue
+    if (!wgrad_wave) {
+        const int64_t n_pts = bwd_points(a);
+        if ((int64_t)blk * 4 + p < (n_pts + 31) / 32) load_in_x6_bwd(a, n_pts, (int64_t)blk * 4 + p, j, h, in_first);
+    }
+#endif
+    fill_images<3, AUX_C2B>(img, c2b, a.W);
+    if (threadIdx.x < X6_ZBLK_ELEMS / 4) reinterpret_cast<u32x2*>(img + X6_ZBLK)[threadIdx.x] = u32x2{0u, 0u};
     if (threadIdx.x < 8) flags[threadIdx.x] = 0;
     __syncthreads();
+    PRO_STAMP(1, 1);
 
-    const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
     WgradX6 g;   // defined (and live) on the wgrad waves only
     if (wgrad_wave) {
         bwd_wgrad_role<QUANT>(a, img, stA, stG, flags + p, flags + 4 + p, p, lane, g, blk, nblk);
     } else {
         QuantRec aq{};
         if constexpr (QUANT) aq = *a.aq;
-        bwd_chain_role<QUANT, SAVED>(a, img, stA, stG, flags + p, flags + 4 + p, p, lane, aq, blk, nblk, c2b);
+        bwd_chain_role<QUANT, SAVED>(a, img, stA, stG, flags + p, flags + 4 + p, p, lane, aq, blk, nblk, c2b, in_first);
     }
 
     // ---- block reduction of the wgrad waves' tiles, one global flush per block. Each wgrad wave
@@ -1292,6 +1372,7 @@ __global__ void __launch_bounds__(512, 1) mlp_bwd_x6cg_kernel(MlpBwdJobs jobs) {
     if (jobs.det_ws) {   // deterministic: the block's image, reduced over blocks in order by mlp_wgrad_reduce
         float* dst = jobs.det_ws + (size_t)blockIdx.x * GW_TOTAL;
         for (int i = threadIdx.x; i < GW_TOTAL; i += blockDim.x) dst[i] = sum4(i);
+        PRO_END(1);
         return;
     }
     // one loop per matrix: a pointer chosen per index would be a dynamically indexed private array
@@ -1306,6 +1387,7 @@ __global__ void __launch_bounds__(512, 1) mlp_bwd_x6cg_kernel(MlpBwdJobs jobs) {
     flush(a.G.c0, GW_C0, GW_C1 - GW_C0);
     flush(a.G.c1, GW_C1, GW_C2 - GW_C1);
     flush(a.G.c2, GW_C2, GW_TOTAL - GW_C2);
+    PRO_END(1);
 }
 
 // Deterministic weight-gradient reduction: value i of a net's gradient image summed over the net's
@@ -1327,6 +1409,22 @@ __global__ void __launch_bounds__(256) mlp_wgrad_reduce_kernel(const float* __re
     else G.c2[i - GW_C2] += s;
 }
 
+// nerf_mlp_weight_image (debug): one block runs the kernels' prologue and copies its image out, the three
+// pieces one after the other, pads included (their contents are unspecified)
+__global__ void __launch_bounds__(kFillThreads) mlp_weight_image_kernel(nerf_mlp_weights W, uint16_t* __restrict__ out) {
+    __shared__ __attribute__((aligned(16))) __bf16 img[3 * IM_PIECE];
+    fill_images<3, AUX_NONE>(img, nullptr, W);
+    __syncthreads();
+    const uint16_t* src = reinterpret_cast<const uint16_t*>(img);
+    for (int i = threadIdx.x; i < 3 * IM_PIECE; i += kFillThreads) out[i] = src[i];
+}
+
+int launch_mlp_weight_image(const nerf_mlp_weights& W, void* d_out, hipStream_t stream) {
+    hipLaunchKernelGGL(mlp_weight_image_kernel, dim3(1), dim3(kFillThreads), 0, stream, W, static_cast<uint16_t*>(d_out));
+    NERF_CHECK_LAUNCH("mlp_weight_image");
+    return NERF_OK;
+}
+
 // every element index the kernels form (feat, sh, raw/graw, geo/dgeo/dsh, dfeat) stays below 2^31
 static bool fits_u32(const MlpArgs& a) {
     const int64_t lim = (int64_t)1 << 31;
@@ -1338,11 +1436,11 @@ int launch_mlp_fwd_x6(const MlpArgs& a, hipStream_t stream) {
     NERF_REQUIRE(fits_u32(a), "mlp_fwd(x6): %lld points exceed 32-bit indexing", (long long)a.P);
     NERF_REQUIRE(!a.h3 || !a.aq, "mlp_fwd(x6): saved h3 with A-CAQ (its backward recomputes)");
     const int64_t tiles = (a.P + 31) / 32;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 15) / 16, 256));
     if (a.aq)
-        hipLaunchKernelGGL(mlp_fwd_x6_kernel<true>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+        hipLaunchKernelGGL(mlp_fwd_x6_kernel<true>, dim3((unsigned)blocks), dim3(1024), 0, stream, a);
     else
-        hipLaunchKernelGGL(mlp_fwd_x6_kernel<false>, dim3((unsigned)blocks), dim3(512), 0, stream, a);
+        hipLaunchKernelGGL(mlp_fwd_x6_kernel<false>, dim3((unsigned)blocks), dim3(1024), 0, stream, a);
     NERF_CHECK_LAUNCH("mlp_fwd(x6)");
     return NERF_OK;
 }
@@ -1351,8 +1449,8 @@ int launch_mlp_fwd_x6(const MlpArgs& a, hipStream_t stream) {
 int launch_mlp_fwd_x6_rays(const MlpArgs& a, const int32_t* ray_ix, hipStream_t stream) {
     NERF_REQUIRE(fits_u32(a), "mlp_fwd_rays: %lld points exceed 32-bit indexing", (long long)a.P);
     const int64_t tiles = (a.P + 31) / 32;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
-    hipLaunchKernelGGL((mlp_fwd_x6_kernel<false, const int32_t*>), dim3((unsigned)blocks), dim3(512), 0, stream, a,
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 15) / 16, 256));
+    hipLaunchKernelGGL((mlp_fwd_x6_kernel<false, const int32_t*>), dim3((unsigned)blocks), dim3(1024), 0, stream, a,
                        ray_ix);
     NERF_CHECK_LAUNCH("mlp_fwd_rays");
     return NERF_OK;
@@ -1427,29 +1525,7 @@ int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_
 // the unrounded h3) and sigma is the unrounded fp32 accumulator o[0]. Same tile orientation, loaders,
 // point order and epilogue as the x6 kernel; no A-CAQ record, no geo output, no saved h3.
 
-// Piece 0 of fill_images' image (the C2 rows are kept: rows 3..15 are W1's zero rows below)
-__device__ inline void fill_image_bf16(__bf16* img, const nerf_mlp_weights& W) {
-    for (int base = threadIdx.x; base < L_END; base += kFillRound * blockDim.x) {
-        float v[kFillRound];
-#pragma unroll
-        for (int u = 0; u < kFillRound; ++u) {
-            const int idx = base + u * (int)blockDim.x;
-            v[u] = idx < L_END ? image_value(idx, W) : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < kFillRound; ++u) {
-            const int idx = base + u * (int)blockDim.x;
-            if (idx >= L_END) continue;
-            int off;
-            if (idx < L_W1) off = IM_W0 + (idx >> 5) * S32 + (idx & 31);
-            else if (idx < L_C0) { const int k = idx - L_W1; off = IM_W1 + (k >> 6) * S64 + (k & 63); }
-            else if (idx < L_C1) { const int k = idx - L_C0; off = IM_C0 + (k >> 5) * S32 + (k & 31); }
-            else if (idx < L_C2) { const int k = idx - L_C1; off = IM_C1 + (k >> 6) * S64 + (k & 63); }
-            else { const int k = idx - L_C2; off = IM_C2 + (k >> 6) * S64 + (k & 63); }
-            img[off] = (__bf16)v[u];
-        }
-    }
-}
+// The image: piece 0 of fill_images' (fill_images<1, ..>; the C2 rows are kept: rows 3..15 are W1's zero rows below)
 
 // 8 values of an operand fragment rounded to bf16 (element i = half (i & 1) of dword i >> 1)
 __device__ __forceinline__ u32x4 pack8(float v0, float v1, float v2, float v3, float v4, float v5, float v6, float v7) {
@@ -1525,8 +1601,7 @@ template <bool PK, typename... RayIx>
 __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a, RayIx... ray_ix) {
     __shared__ __attribute__((aligned(16))) __bf16 img[IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
-    fill_image_bf16(img, a.W);
-    fill_c2f(c2f, a.W);
+    fill_images<1, AUX_C2F>(img, c2f, a.W);
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 31, m = j, h = lane >> 5;
     const int64_t n_tiles = (a.P + 31) / 32;
@@ -1635,6 +1710,16 @@ extern "C" int nerf_x6cg_prof(unsigned long long* out12) {
     const unsigned long long zero[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     if (hipMemcpyToSymbol(HIP_SYMBOL(cg_prof), zero, sizeof(cg_prof)) != hipSuccess) return 1;
     return hipMemcpyToSymbol(HIP_SYMBOL(cg_stage_wait), zero, sizeof(cg_stage_wait)) == hipSuccess ? 0 : 1;
+}
+#endif
+
+#ifdef NERF_X6_PROLOGUE_PROF
+// diagnostic builds only: the per-block stamps of the launches since the last call (2 kernels x 512 blocks x 5), reset
+extern "C" int nerf_x6_prologue_prof(unsigned long long* out) {
+    if (hipMemcpyFromSymbol(out, HIP_SYMBOL(pro_prof), sizeof(pro_prof)) != hipSuccess) return 1;
+    void* d = nullptr;
+    if (hipGetSymbolAddress(&d, HIP_SYMBOL(pro_prof)) != hipSuccess) return 1;
+    return hipMemset(d, 0, sizeof(pro_prof)) == hipSuccess ? 0 : 1;
 }
 #endif
 
