@@ -1051,6 +1051,37 @@ int nerf_mlp_fwd_bf16_pkbf_rays(const uint32_t* d_featw, int64_t feat_stride_poi
                                 const uint8_t* d_keep, int64_t n_points,
                                 const nerf_mlp_weights* weights, float* d_raw, void* stream);
 
+/* ---- Launches sized on the device (csrc/hashgrid_pkbf.hip, csrc/field_x6.hip) ----
+ * Additive entries (the ABI version stays 12). A grid march's list has its length in device memory (the last
+ * element of nerf_march_count's offsets); these entries read it there, so that no host read sits between the
+ * march's count and its field. Each takes (d_total, base, capacity) where its host-sized twin takes n_points: the
+ * per-point buffers hold `capacity` points and start at the slice's first point, which is point `base` of the
+ * list, and the launch covers n = clamp(*d_total - base, 0, capacity) points (d_total: one int32 in device
+ * memory, read by the kernel; a negative total gives n = 0). The grid is fixed by the capacity. Every point p < n
+ * gets, in every bit, what the twin gives at n_points = n; nothing at or beyond entry n of any output is written,
+ * and with n = 0 no point is read. capacity = 0 launches nothing and accepts NULL per-point buffers.
+ *
+ * nerf_hash_encode_fwd_pkbf_dev, nerf_hash_encode_fwd_half_pkbf_dev: nerf_hash_encode_fwd_pkbf and
+ *   nerf_hash_encode_fwd_half_pkbf. max_blocks caps the grid (the kernel walks the blocks of the twin's grid for n
+ *   points with a grid stride, level-major); 0 is the default, 8 blocks per compute unit. The capacity must fit one
+ *   launch (its twin's grid below 2^24 blocks).
+ * nerf_mlp_fwd_bf16_pkbf_rays_dev: nerf_mlp_fwd_bf16_pkbf_rays. The feature indexing of `capacity` points stays
+ *   below 2^31. THE CALLER GUARANTEES 0 <= d_ray_of[p] < n_rays for every p < n. */
+int nerf_hash_encode_fwd_pkbf_dev(const float* d_xyz, const int32_t* d_total, int64_t base, int64_t capacity,
+                                  int max_blocks, const float* bbox_min3, const float* bbox_max3,
+                                  const float* level_res, int n_levels, int log2_T, const float* const* d_tables,
+                                  uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                  uint8_t* d_keep, void* stream);
+int nerf_hash_encode_fwd_half_pkbf_dev(const float* d_xyz, const int32_t* d_total, int64_t base, int64_t capacity,
+                                       int max_blocks, const float* bbox_min3, const float* bbox_max3,
+                                       const float* level_res, int n_levels, int log2_T, const void* d_half,
+                                       uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                       uint8_t* d_keep, void* stream);
+int nerf_mlp_fwd_bf16_pkbf_rays_dev(const uint32_t* d_featw, int64_t feat_stride_point, int64_t feat_stride_level,
+                                    const float* d_sh_rec, const int32_t* d_ray_of, int64_t n_rays,
+                                    const uint8_t* d_keep, const int32_t* d_total, int64_t base, int64_t capacity,
+                                    const nerf_mlp_weights* weights, float* d_raw, void* stream);
+
 /* Debug: the bf16 weight image that every block of the fp32-accurate MLP kernels builds in its prologue
  * (csrc/field_x6.hip), copied out by one block that runs that prologue. d_out receives 3 x 11,136 bf16
  * elements (66,816 B): piece k (k = 0, 1, 2; v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1), round to

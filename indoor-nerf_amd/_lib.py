@@ -282,6 +282,13 @@ SIGNATURES = {
                                c_vp],
     "nerf_mlp_fwd_bf16_pkbf_rays": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_i64, ctypes.POINTER(MlpWeights),
                                     c_vp, c_vp],
+    # launches sized on the device: (d_total, base, capacity[, max_blocks]) in place of n_points
+    "nerf_hash_encode_fwd_pkbf_dev": [c_vp, c_vp, c_i64, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_int, c_int,
+                                      ctypes.POINTER(c_vp), c_vp, c_i64, c_i64, c_vp, c_vp],
+    "nerf_hash_encode_fwd_half_pkbf_dev": [c_vp, c_vp, c_i64, c_i64, c_int, c_f32p, c_f32p, c_f32p, c_int, c_int, c_vp,
+                                           c_vp, c_i64, c_i64, c_vp, c_vp],
+    "nerf_mlp_fwd_bf16_pkbf_rays_dev": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64,
+                                        ctypes.POINTER(MlpWeights), c_vp, c_vp],
     # debug: the MLP kernels' prologue image (csrc/field_x6.hip fill_images), 3 x 11,136 bf16 elements
     "nerf_mlp_weight_image": [ctypes.POINTER(MlpWeights), c_vp, c_vp],
 }

@@ -26,6 +26,8 @@ int launch_mlp_fwd_bf16(const MlpArgs& a, bool packed, hipStream_t stream);
 int launch_mlp_bwd_x6(const MlpArgs* jobs, int n_jobs, float* det_ws, hipStream_t stream);
 int launch_mlp_fwd_x6_rays(const MlpArgs& a, const int32_t* ray_ix, hipStream_t stream);
 int launch_mlp_fwd_bf16_rays(const MlpArgs& a, bool packed, const int32_t* ray_ix, hipStream_t stream);
+int launch_mlp_fwd_bf16_pkbf_rays_dev(const MlpArgs& a, const int32_t* ray_ix, const int32_t* d_total, int64_t base,
+                                      hipStream_t stream);
 int launch_mlp_weight_image(const nerf_mlp_weights& W, void* d_out, hipStream_t stream);
 
 static int fill_args(MlpArgs& a, const float* d_feat, int64_t sp, int64_t sl, const float* d_sh, int64_t sh_stride,
@@ -214,6 +216,33 @@ extern "C" int nerf_mlp_fwd_bf16_pkbf_rays(const uint32_t* d_featw, int64_t feat
                                            const nerf_mlp_weights* weights, float* d_raw, void* stream) {
     return mlp_fwd_rays("mlp_fwd_bf16_pkbf_rays", 2, reinterpret_cast<const float*>(d_featw), feat_stride_point,
                         feat_stride_level, d_sh_rec, d_ray_of, n_rays, d_keep, n_points, weights, d_raw, stream);
+}
+
+// nerf_mlp_fwd_bf16_pkbf_rays with the point count read on the device: the buffers hold `capacity`
+// points from the slice's first point, whose number in the list is `base`; clamp(*d_total - base, 0, capacity) points
+// are evaluated and the rows of d_raw at or beyond that are not written.
+extern "C" int nerf_mlp_fwd_bf16_pkbf_rays_dev(const uint32_t* d_featw, int64_t feat_stride_point,
+                                               int64_t feat_stride_level, const float* d_sh_rec,
+                                               const int32_t* d_ray_of, int64_t n_rays, const uint8_t* d_keep,
+                                               const int32_t* d_total, int64_t base, int64_t capacity,
+                                               const nerf_mlp_weights* w, float* d_raw, void* stream) {
+    const char* who = "mlp_fwd_bf16_pkbf_rays_dev";
+    NERF_REQUIRE(capacity >= 0 && base >= 0 && n_rays >= 0, "%s: capacity %lld, base %lld, n_rays %lld", who,
+                 (long long)capacity, (long long)base, (long long)n_rays);
+    NERF_REQUIRE(w && w->w0 && w->w1 && w->c0 && w->c1 && w->c2, "%s: null weight pointer", who);
+    NERF_REQUIRE(d_total, "%s: null count", who);
+    if (capacity == 0) return NERF_OK;
+    NERF_REQUIRE(d_featw && d_sh_rec && d_ray_of && d_raw, "%s: null arg", who);
+    NERF_REQUIRE(n_rays >= 1, "%s: a capacity of %lld points needs n_rays >= 1", who, (long long)capacity);
+    NERF_REQUIRE((int64_t)kShRecord * n_rays < ((int64_t)1 << 31), "%s: %lld rays exceed 32-bit indexing", who,
+                 (long long)n_rays);
+    NERF_REQUIRE(((uintptr_t)d_sh_rec & 15) == 0, "%s: SH records must be 16-B aligned", who);
+    MlpArgs a{};
+    int rc = fill_args(a, reinterpret_cast<const float*>(d_featw), feat_stride_point, feat_stride_level, d_sh_rec, 0,
+                       nullptr, 1, d_keep, capacity, w);
+    if (rc) return rc;
+    a.raw = d_raw;
+    return launch_mlp_fwd_bf16_pkbf_rays_dev(a, d_ray_of, d_total, base, as_stream(stream));
 }
 
 extern "C" int nerf_mlp_bwd_q(const float* d_feat, int64_t feat_stride_point, int64_t feat_stride_level,

@@ -1570,6 +1570,32 @@ __device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, boo
     return u32x4{g0.x, g0.y, g1.x, g1.y};
 }
 
+// The point count of a launch read on the device (nerf_mlp_fwd_bf16_pkbf_rays_dev): rides behind the
+// ray index in mlp_fwd_bf16_kernel's trailing parameters. The launch covers clamp(*total - base, 0, capacity) points.
+struct DevCount {
+    const int32_t* total;
+    int64_t base, capacity;
+};
+
+// ... the SH operand does not depend on where the count comes from
+__device__ __forceinline__ u32x4 load_sh_bf16(const MlpArgs& a, uint32_t pt, bool valid, int h, const int32_t* ray_ix,
+                                              DevCount) {
+    return load_sh_bf16(a, pt, valid, h, ray_ix);
+}
+
+// Whether this block of mlp_fwd_bf16_kernel has a tile to walk. The host-sized launches: always (a.P is the launch's
+// count and the grid was cut to it; no instruction). With a DevCount: a.P becomes the device value, and a block of
+// the capacity's grid whose first tile lies beyond it (every block when the count is 0) has none. Uniform over the
+// block.
+template <typename... Tail>
+__device__ __forceinline__ bool mlp_block_has_tiles(MlpArgs&, Tail...) { return true; }
+__device__ __forceinline__ bool mlp_block_has_tiles(MlpArgs& a, const int32_t*, DevCount c) {
+    int64_t n = (int64_t)*c.total - c.base;
+    n = n < 0 ? 0 : (n > c.capacity ? c.capacity : n);
+    a.P = n;
+    return (int64_t)blockIdx.x * (blockDim.x >> 6) < (n + 31) / 32;
+}
+
 // Packed bf16 features (mlp_fwd_bf16_kernel<true>, nerf_mlp_fwd_bf16_pkbf): a.feat holds one word
 // {bf16 f0, bf16 f1} per (point, level), written by the packed encoder (hashgrid_pkbf.hip) with pk_bf16, a.sp / a.sl
 // in words. Lane (j, h) loads the words of levels 8c + 4q + 2h + e and uses them as they are:
@@ -1596,11 +1622,15 @@ __device__ __forceinline__ void load_x_pkbf(const MlpArgs& a, uint32_t pt, bool 
 // measured 37.7 us against 35.8 us per 786,432 points without it.
 // PK: the features are packed bf16 words (load_x_pkbf) and layer 0 takes them without a conversion; <false> is
 // the kernel as it was (the same instructions).
-// RayIx: as mlp_fwd_x6_kernel's: empty, or the ray index of nerf_mlp_fwd_bf16_rays / nerf_mlp_fwd_bf16_pkbf_rays.
+// RayIx: as mlp_fwd_x6_kernel's: empty, or the ray index of nerf_mlp_fwd_bf16_rays / nerf_mlp_fwd_bf16_pkbf_rays, or
+// the ray index and a DevCount (nerf_mlp_fwd_bf16_pkbf_rays_dev): the tile loop is the same, a.P is then the count
+// read on the device and a block without a tile returns before the weight image (mlp_block_has_tiles: before the
+// barrier, uniform over the block).
 template <bool PK, typename... RayIx>
 __global__ void __launch_bounds__(512, 2) mlp_fwd_bf16_kernel(MlpArgs a, RayIx... ray_ix) {
     __shared__ __attribute__((aligned(16))) __bf16 img[IM_PIECE];
     __shared__ __attribute__((aligned(16))) float c2f[C2F_FLOATS];
+    if (!mlp_block_has_tiles(a, ray_ix...)) return;
     fill_images<1, AUX_C2F>(img, c2f, a.W);
     __syncthreads();
     const int lane = threadIdx.x & 63, j = lane & 31, m = j, h = lane >> 5;
@@ -1697,6 +1727,21 @@ int launch_mlp_fwd_bf16_rays(const MlpArgs& a, bool packed, const int32_t* ray_i
     const dim3 grid((unsigned)blocks), block(512);
     if (packed) hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, const int32_t*>), grid, block, 0, stream, a, ray_ix);
     else hipLaunchKernelGGL((mlp_fwd_bf16_kernel<false, const int32_t*>), grid, block, 0, stream, a, ray_ix);
+    NERF_CHECK_LAUNCH(who);
+    return NERF_OK;
+}
+
+// nerf_mlp_fwd_bf16_pkbf_rays_dev: the packed launch above with the count read on the device. a.P is the capacity:
+// it sizes the grid and bounds the 32-bit indexing (the device count is at most the capacity).
+int launch_mlp_fwd_bf16_pkbf_rays_dev(const MlpArgs& a, const int32_t* ray_ix, const int32_t* d_total, int64_t base,
+                                      hipStream_t stream) {
+    const char* who = "mlp_fwd_bf16_pkbf_rays_dev";
+    NERF_REQUIRE(fits_u32(a), "%s: capacity %lld exceeds 32-bit indexing", who, (long long)a.P);
+    const int64_t tiles = (a.P + 31) / 32;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((tiles + 7) / 8, 256 * 2));
+    const DevCount c{d_total, base, a.P};
+    hipLaunchKernelGGL((mlp_fwd_bf16_kernel<true, const int32_t*, DevCount>), dim3((unsigned)blocks), dim3(512), 0,
+                       stream, a, ray_ix, c);
     NERF_CHECK_LAUNCH(who);
     return NERF_OK;
 }

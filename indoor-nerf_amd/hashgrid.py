@@ -663,14 +663,19 @@ class HashEmbedder(nn.Module):
             st["key"] = key
         return st["buf"]
 
-    def encode_into(self, xyz, feat, sp, sl, keep, row0=0, half=False, packed=False):
+    def encode_into(self, xyz, feat, sp, sl, keep, row0=0, half=False, packed=False, count=None):
         """Forward gather into caller-allocated feat/keep on the path this forward needs: plain,
         fake-quantized (training / STE) or int-packed (eval-mode quantizers). row0: the points land in
         rows row0 .. row0 + n of feat (level-major, point stride sp, level stride sl) and keep.
         half (forward-only rendering): gather from half_tables() instead of the fp32 tables.
         packed (forward-only rendering): feat is an int32 buffer of packed bf16 words, one
         {bf16 f0, bf16 f1} per (point, level), and sp, sl count words (nerf_hash_encode_fwd_pkbf, with half
-        nerf_hash_encode_fwd_half_pkbf)."""
+        nerf_hash_encode_fwd_half_pkbf).
+        count = (total, base) (forward-only rendering; with packed): xyz holds the capacity of a slice
+        whose first point is point `base` of a list of *total points (total: one int32 element in device memory);
+        the _dev twin of the packed entry encodes clamp(total - base, 0, capacity) points and reads the count itself."""
+        if count is not None and not packed:
+            raise ValueError("encode_into: a device count needs packed features")
         if half and self.quantization_active():
             raise ValueError(HALF_ACAQ)
         if packed and self.quantization_active():
@@ -682,6 +687,17 @@ class HashEmbedder(nn.Module):
             raise ValueError("encode_into: rows out of the feature / keep buffers")
         fp = _lib.ptr_at(feat, sp * row0, "feat", dtype=fdt)
         kp = _lib.ptr_at(keep, row0, "keep", dtype=torch.bool)
+        if count is not None:
+            size = (_lib.ptr(count[0], "total", dtype=torch.int32), int(count[1]), P, 0)
+            if half:
+                tables = _lib.ptr(self.half_tables(), "half_tables", dtype=torch.uint8)
+            else:
+                join_tables(xyz.device)
+                tables = _lib.ptr_array(self.tables())
+            _lib.call("nerf_hash_encode_fwd_half_pkbf_dev" if half else "nerf_hash_encode_fwd_pkbf_dev",
+                      _lib.ptr(xyz, "xyz"), *size, meta["bmin"], meta["bmax"], meta["res"], self.n_levels,
+                      meta["log2_T"], tables, fp, sp, sl, kp, _lib.stream())
+            return
         if half:
             _lib.call("nerf_hash_encode_fwd_half_pkbf" if packed else "nerf_hash_encode_fwd_half", _lib.ptr(xyz, "xyz"),
                       P, meta["bmin"], meta["bmax"], meta["res"], self.n_levels, meta["log2_T"],

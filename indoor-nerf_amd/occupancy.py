@@ -69,6 +69,8 @@ class OccupancyGrid:
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self._bmin, self._bmax = _lib.host_f32(bmin), _lib.host_f32(bmax)
         self.bits = torch.zeros(self.n_words, dtype=torch.int32, device=self.device)
+        # (points evaluated, points total) of the last field call. The first is an int, or, after a device-sized march
+        # (DESIGN.md §23), a list of int32 [1] device views into the lists' offsets that last_counts() sums and replaces
         self._last = (0, 0)
 
     def _bits(self, t=None):
@@ -97,7 +99,13 @@ class OccupancyGrid:
         return float(self.mask().float().mean())
 
     def last_counts(self):
-        """(points evaluated, points total) of the most recent field call through this grid."""
+        """(points evaluated, points total) of the most recent field call through this grid. After a device-sized
+        march the evaluated count is still in device memory, one int32 element per list: it is read
+        here, once, when it is asked for."""
+        n, total = self._last
+        if not isinstance(n, int):
+            n = int(torch.cat([c.reshape(1) for c in n]).sum().item())
+            self._last = (n, total)
         return self._last
 
     # ---- kernels ------------------------------------------------------------------------------
@@ -220,10 +228,11 @@ class OccupancyGrid:
         return hit, span, rows, rays_c
 
     # ---- grid ray marching (csrc/march.hip) ----------------------------------------
-    def _march_count(self, rays, K, k0=None, k1=None, alive=None, dirs=True):
+    def _march_count(self, rays, K, k0=None, k1=None, alive=None, dirs=True, sized="host"):
         """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n). With a
         lattice range [k0, k1) (and alive, uint8 [R], or None for every ray): nerf_slab_march_count over that range
-        of the rays alive. dirs=False: rays_d is not written (None)."""
+        of the rays alive. dirs=False: rays_d is not written (None). sized="device" (DESIGN.md §23):
+        n is the device element offsets[R:R + 1], int32 [1], and the host reads nothing."""
         from .render import _linspace
         rays = _packed_rows(rays, "march")
         K = check_march_samples(K, "OccupancyGrid.march")
@@ -244,15 +253,23 @@ class OccupancyGrid:
                       self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
                       _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d", allow_none=True),
                       _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
-            n = int(offsets[R].item())     # one 4-byte host read sizes the list
+            if sized != "device":
+                n = int(offsets[R].item())     # one 4-byte host read sizes the list
+        if sized == "device":
+            n = offsets[R:R + 1]
         return rays, t, counts, offsets, rays_d, n
 
     def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None, index=False):
         """nerf_march_write of the list _march_count sized; with the same [k0, k1): nerf_slab_march_write.
         index: the nerf_rays_ write; the fourth result is then ray_c int32 [n], the row of each
-        entry's ray in `rays`, and no SH row is formed."""
+        entry's ray in `rays`, and no SH row is formed. n a device element (_march_count sized="device", DESIGN.md
+        §23): the list is allocated at its capacity R (k1 - k0), the worst case, and the write is told that capacity
+        in place of the count: the kernel bounds its stores by the capacity and takes every position from counts and
+        offsets, so entries [0, *n) are written exactly as in the host-sized call and nothing beyond them."""
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
         f = dict(device=dev, dtype=torch.float32)
+        if torch.is_tensor(n):
+            n = R * ((K if k1 is None else int(k1)) - (0 if k0 is None else int(k0)))
         pts_c, z_c, dist_c = torch.empty(n, 3, **f), torch.empty(n, **f), torch.empty(n, **f)
         if index:
             last = torch.empty(n, device=dev, dtype=torch.int32)

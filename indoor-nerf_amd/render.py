@@ -402,7 +402,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 perturb=0., N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False,
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
-                table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None, march_sh=None):
+                table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None, march_sh=None,
+                march_sizes=None):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -447,9 +448,21 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     index (4 B) instead of its SH4 row (64 B); one SH record per ray is formed once per chunk (nerf_ray_sh_records) and
     the MLP reads it through the index (the _rays entry of the call's precision). The result is bit for bit the march
     without it, in every entry. Composes with march_stop=, mlp_precision=, table_precision=, feature_precision= and
-    render's ray_bounds=. None and "rows" are the call without it: the same launches, the same buffers."""
+    render's ray_bounds=. None and "rows" are the call without it: the same launches, the same buffers.
+    march_sizes (None, "host" or "device"; with march=, march_sh="rays", mlp_precision="bf16" and
+    feature_precision="bf16"): "device" keeps the length of every packed list in device memory. The
+    lists are allocated at their capacity (40 B per lattice sample of the chunk, or of the slab with march_stop), the
+    encoder and the MLP read the count themselves (the _dev entries) over ceil(capacity / march_points) slices, and
+    every slab of a chunk is written, evaluated, composited and advanced back to back: the host reads nothing and no
+    launch depends on a count. The result is bit for bit the call without it, in every entry. With retraw the packed
+    entries are views of the first n rows, which costs one read after the chunk's last launch. Composes with
+    march_stop=, table_precision=, march_points= and render's ray_bounds=. None and "host" are the call without it:
+    the same launches, the same buffers."""
+    # march_sizes is passed only when given: tests/test_field_request.py pins this call's eight positional arguments
+    # and empty keywords for a call without it (the same in render())
     opts = sparse_field.field_options("render_rays", march, march_sh, march_stop, march_stop_slab, mlp_precision,
-                                      table_precision, feature_precision)
+                                      table_precision, feature_precision,
+                                      **({} if march_sizes is None else dict(march_sizes=march_sizes)))
     nets = [network_fn] + ([] if network_fine is None else [network_fine])
     if opts.half:
         sparse_field.check_table_nets(nets, embed_fn)
@@ -459,7 +472,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
         return _render_rays_march(ray_batch, network_fn, network_query_fn, march, march_samples, march_points, opts,
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
-                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop)
+                                  predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
+                                  device_sizes=sparse_field.device_sized(march_sizes))
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -600,12 +614,15 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, opts, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None):
+                       predict_normals=False, occupancy=None, early_stop=None, device_sizes=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing. opts: the call's FieldOptions. With
     opts.stop (march_stop) the same in slabs (_march_slabs). opts.by_ray (march_sh="rays", DESIGN.md
     §21): the write leaves a ray index in place of the SH rows, and the field reads the SH records of the chunk's
-    packed rays through it."""
+    packed rays through it. device_sizes (march_sizes="device", DESIGN.md §23): the list's length stays on the device;
+    the list is allocated at its capacity R K, the composite is given that capacity as its list bound (it clamps a
+    segment into the list, and every offset is at most the true length, which is at most the capacity) and the field
+    runs whenever the capacity is not 0."""
     run_fn = network_fn if network_fine is None else network_fine
     K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
                      predict_normals, occupancy, early_stop)
@@ -614,28 +631,35 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     by_ray = opts.by_ray
     records = []   # by_ray: the SH records of the chunk's packed rays, formed before its first field call
 
-    def field(rays, pts_c, sh_c):
+    def field(rays, pts_c, sh_c, total=None):
         """The field on a packed list of n > 0 points (by_ray: sh_c is the points' ray index into `rays`, the same
-        packed rows in every slab of a chunk)."""
+        packed rows in every slab of a chunk). total (device_sizes): the list's length, int32 [1] on the device; the
+        buffers then hold the list's capacity."""
         if by_ray:
             if not records:
                 records.append(grid._ray_sh_records(rays))
-            march = sparse_field.MarchList(None, march_points, ray_c=sh_c, sh_rec=records[0])
+            march = sparse_field.MarchList(None, march_points, ray_c=sh_c, sh_rec=records[0], total=total,
+                                           capacity=None if total is None else pts_c.shape[0])
         else:
             march = sparse_field.MarchList(sh_c, march_points)
         return _query(network_query_fn, pts_c, rays[:, 8:11], run_fn, opts.request(march=march))[0]
 
     if opts.stop is not None:
-        ret = _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw)
+        ret = _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw, device_sizes)
         if DEBUG:
             check_numerics(ret)
         return ret
-    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K)
+    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K, sized="device" if device_sizes else "host")
     R, dev = rays.shape[0], rays.device
     pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, index=by_ray)
-    grid._last = (n, R * K)
     f = dict(device=dev, dtype=torch.float32)
-    raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
+    if device_sizes:
+        grid._last = ([n], R * K)        # the count as device elements, one per list: last_counts() reads them when asked
+        total, n = n, pts_c.shape[0]     # from here on n is the capacity: the bound every launch is given
+        raw = field(rays, pts_c, sh_c, total) if n > 0 else torch.empty(0, 4, **f)
+    else:
+        grid._last = (n, R * K)
+        raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
     rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
     if R > 0:
         _lib.call("nerf_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z_c, "z_c"), _lib.ptr(dist_c, "dist_c"),
@@ -645,28 +669,36 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     # restated for zero rays in _no_rays_result: keep the two in step
     ret = dict(rgb_map=rgb_map, depth_map=depth_map, acc_map=acc_map, march_samples=counts, rays_d=rays_d)
     if retraw:
+        if device_sizes:    # the one read of the chunk, after its last launch: the packed entries as views [:n]
+            n = int(total.item())
+            raw, pts_c, z_c = raw[:n], pts_c[:n], z_c[:n]
         ret.update(raw=raw, pts=pts_c, z_vals=z_c, march_offsets=offsets)
     if DEBUG:
         check_numerics(ret)
     return ret
 
 
-def _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw):
+def _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw, device_sizes=False):
     """The march of _render_rays_march with march_stop, opts.stop = (eps, slab): the lattice front to
     back in slabs; per slab the packed list of the rays alive (one 4-byte host read sizes it), field(rays, pts_c,
     sh_c) on it, its compositing into the per-ray state and, unless it is the last, the stopping rule. A slab with
     an empty list skips the field and its launches (the last slab's compositing always runs: it writes the maps).
-    opts.by_ray: every slab's write leaves the ray index in place of the SH rows."""
+    opts.by_ray: every slab's write leaves the ray index in place of the SH rows.
+    device_sizes (march_sizes="device"): no read; every slab's list is allocated at its capacity
+    R (k1 - k0), and every slab is evaluated, composited (first = slab 0) and, unless it is the last, advanced, an
+    empty one too: an empty segment leaves a ray's state, tau, alive and stop as they are, so the bits are those of
+    the loop that skips."""
     from .early_stop import tau_max_of
     (eps, Ks), by_ray = opts.stop, opts.by_ray
     tau_max = tau_max_of(eps)
     rays = tau = alive = stops = state = rays_d = None
     rgb_map = depth_map = acc_map = None
-    slabs, counts_all, evaluated, first = [], [], 0, True
+    slabs, counts_all, evaluated, first, totals = [], [], 0, True, []
     for k0 in range(0, K, Ks):
         k1 = min(k0 + Ks, K)
         rays, t, counts, offsets, dirs, n = grid._march_count(ray_batch if rays is None else rays, K, k0, k1, alive,
-                                                              dirs=rays_d is None)
+                                                              dirs=rays_d is None,
+                                                              sized="device" if device_sizes else "host")
         R, dev = rays.shape[0], rays.device
         f = dict(device=dev, dtype=torch.float32)
         if rays_d is None:      # slab 0: the state every later slab carries
@@ -677,8 +709,14 @@ def _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw):
                 state = torch.empty(R, 6, device=dev, dtype=torch.float64)
             stops = torch.full((R,), K, device=dev, dtype=torch.int32)
         pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, k0, k1, index=by_ray)
-        raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
-        evaluated += n
+        if device_sizes:
+            totals.append(n)
+            total, n = n, pts_c.shape[0]     # from here on n is the capacity: the bound every launch is given
+            raw = field(rays, pts_c, sh_c, total) if n > 0 else torch.empty(0, 4, **f)
+            first = k0 == 0
+        else:
+            raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
+            evaluated += n
         counts_all.append(counts)
         if retraw:
             slabs.append((offsets, raw, pts_c, z_c))
@@ -697,7 +735,12 @@ def _march_slabs(ray_batch, grid, K, opts, field, white_bkgd, retraw):
                       _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n, k1, tau_max,
                       _lib.ptr(tau, "tau"), _lib.ptr(alive, "alive", torch.uint8), _lib.ptr(stops, "stop", torch.int32),
                       _lib.stream())
-    grid._last = (evaluated, rays.shape[0] * K)
+    # host-sized: the evaluated count, an int; device-sized: one device element per slab (views into the slabs' offsets,
+    # which they keep alive until the next march through this grid or until last_counts() resolves them)
+    grid._last = (totals if device_sizes else evaluated, rays.shape[0] * K)
+    if device_sizes and retraw:     # the one read of the chunk, after its last launch: the packed entries as views [:n]
+        ns = torch.cat(totals).tolist()
+        slabs = [(o, raw[:m], p[:m], z[:m]) for (o, raw, p, z), m in zip(slabs, ns)]
     total = counts_all[0] if len(counts_all) == 1 else torch.stack(counts_all).sum(0, dtype=torch.int32)
     # restated for zero rays in _no_rays_result: keep the two in step
     ret = dict(rgb_map=rgb_map, depth_map=depth_map, acc_map=acc_map, march_samples=total, rays_d=rays_d,
@@ -870,12 +913,16 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
     spans its own [near', far']. mlp_precision and table_precision go to
     render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
-    §20) and march_sh. retraw is refused with march: the packed entries of several chunks do not
+    §20), march_sh and march_sizes (the one count read per frame of ray_bounds stays).
+    retraw is refused with march: the packed entries of several chunks do not
     concatenate."""
     # render_rays' value checks, also when no chunk reaches it (ray_bounds with every ray missed)
+    # march_sizes only when given, as in render_rays: the pinned call record of tests/test_field_request.py
     opts = sparse_field.field_options("render", kwargs.get("march"), kwargs.get("march_sh"), kwargs.get("march_stop"),
                                       kwargs.get("march_stop_slab", 128), kwargs.get("mlp_precision"),
-                                      kwargs.get("table_precision"), kwargs.get("feature_precision"))
+                                      kwargs.get("table_precision"), kwargs.get("feature_precision"),
+                                      **({} if kwargs.get("march_sizes") is None
+                                         else dict(march_sizes=kwargs["march_sizes"])))
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")

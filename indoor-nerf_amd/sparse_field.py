@@ -24,7 +24,8 @@ NOT_IN_TRAINING = {"occupancy": "the grid is not used in training", "early_stop"
                    "mlp_precision": "the backward recomputes the forward in fp32",
                    "table_precision": "the backward scatters into the fp32 tables",
                    "feature_precision": "the backward reads fp32 features",
-                   "march_sh": "the backward reads per-point SH rows"}
+                   "march_sh": "the backward reads per-point SH rows",
+                   "march_sizes": "the backward needs the list lengths on the host"}
 DEFAULT_MARCH_POINTS = 1 << 21
 
 
@@ -50,13 +51,20 @@ class MarchList:
     """The packed list of a grid march's field call (FieldRequest.march): the SH4 rows of the points'
     rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch. With march_sh="rays" 
     sh_c is None and the list carries the points' ray index, ray_c int32 [n], and one SH record per ray, sh_rec
-    [R, 40] (0 <= ray_c < R: the march's write guarantees it)."""
+    [R, 40] (0 <= ray_c < R: the march's write guarantees it). With march_sizes="device"  the list's
+    buffers hold `capacity` entries and its length is `total`, one int32 element in device memory."""
 
-    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None):
+    total = capacity = None     # a host-sized list: its length is the tensors'
+
+    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None, total=None, capacity=None):
         if (sh_c is None) == (ray_c is None) or (ray_c is None) != (sh_rec is None):
             raise ValueError("march: a request carries either sh_c or (ray_c, sh_rec)")
+        if (total is None) != (capacity is None) or (total is not None and ray_c is None):
+            raise ValueError("march: a device-sized list carries (total, capacity) and a ray index")
         self.sh_c, self.max_points = sh_c, check_march_points(max_points)
         self.ray_c, self.sh_rec = ray_c, sh_rec
+        if total is not None:     # a host-sized list stays the four attributes it was
+            self.total, self.capacity = total, capacity
 
 
 class FieldRequest:
@@ -92,16 +100,47 @@ class FieldRequest:
 
 
 def field_options(prefix, march, march_sh, march_stop, march_stop_slab, mlp_precision, table_precision,
-                  feature_precision):
+                  feature_precision, march_sizes=None):
     """The value checks of the call-level forward-only keywords of `prefix` (render_rays, render), in one fixed
     order -> FieldOptions. The checks that need the call's modules (check_table_nets, check_mlp_nets) follow in the
-    caller."""
+    caller. march_sizes is checked last, against the others' answers; its own answer is not part of
+    FieldOptions: the caller asks device_sized(march_sizes)."""
     by_ray = check_march_sh(march_sh, march, prefix)
     stop = check_march_stop(march_stop, march_stop_slab, march, prefix)
     bf16 = check_mlp_precision(mlp_precision, prefix)
     packed = check_feature_precision(feature_precision, bf16, prefix)
     half = check_table_precision(table_precision, prefix)
+    check_march_sizes(march_sizes, march, by_ray, bf16, packed, prefix)
     return FieldOptions(bf16, half, packed, by_ray, stop)
+
+
+def device_sized(value):
+    """Whether a march_sizes value that check_march_sizes accepted asks for device-sized launches."""
+    return isinstance(value, str) and value == "device"
+
+
+def check_march_sizes(value, march, by_ray, bf16, packed, prefix):
+    """march_sizes of `prefix` (render_rays, render) -> whether the march keeps its list lengths in device memory
+    (DESIGN.md §23); its refusals, one fixed sentence each: an unknown value, "device" without march=, without each
+    of march_sh="rays", mlp_precision="bf16" and feature_precision="bf16" (by_ray, bf16, packed: the answers of their
+    checks), gradients enabled."""
+    if value is None or (isinstance(value, str) and value == "host"):
+        return False
+    if not (isinstance(value, str) and value == "device"):
+        raise ValueError(f"{prefix}: march_sizes must be None, 'host' or 'device', got {value!r}")
+    if march is None:
+        raise ValueError(f"{prefix}: march_sizes='device' needs march= (the sizes are those of a grid march's lists)")
+    if not by_ray:
+        raise ValueError(f"{prefix}: march_sizes='device' needs march_sh='rays' (the device-sized MLP reads SH through "
+                         "the ray index)")
+    if not bf16:
+        raise ValueError(f"{prefix}: march_sizes='device' needs mlp_precision='bf16' (the device-sized MLP is the bf16 "
+                         "forward)")
+    if not packed:
+        raise ValueError(f"{prefix}: march_sizes='device' needs feature_precision='bf16' (the device-sized encoder "
+                         "writes packed bf16 features)")
+    check_forward_only("march_sizes", prefix)
+    return True
 
 
 def check_mlp_precision(value, prefix):
@@ -308,6 +347,8 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     ml = req.march
     by_ray = ml.ray_c is not None
     _begin_field_call("march", inputs.dim() == 2, "packed inputs [n, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
+    if ml.total is not None:
+        return _run_network_packed_dev(inputs, fn, embed_fn, req)
     n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
     if by_ray:
         if tuple(ml.ray_c.shape) != (n,) or ml.sh_rec.dim() != 2 or ml.sh_rec.shape[1] != 40:
@@ -329,6 +370,37 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
         mlp_forward(req, _lib.ptr(feat, "feat", fdt), w * k, None if by_ray else _lib.ptr_at(ml.sh_c, 16 * s0, "sh_c"),
                     _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None,
                     (_lib.ptr_at(ml.ray_c, s0, "ray_c", torch.int32), sh_rec, n_rec) if by_ray else None)
+    return raw
+
+
+def _run_network_packed_dev(inputs, fn, embed_fn, req):
+    """run_network_packed for a device-sized list (march_sizes="device"): inputs [capacity, 3] of which
+    the first *ml.total rows are points -> raw [capacity, 4] with those rows written and the others left as allocated.
+    ceil(capacity / max_points) slices, a number the host knows; slice s covers clamp(total - s m, 0, m) points, read
+    by the kernels (the _dev entries), so an empty slice is launched and does nothing. No host read."""
+    from .field import _weights_struct
+    ml = req.march
+    cap, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
+    if not (req.bf16 and req.packed):
+        raise ValueError("march: a device-sized list needs the bf16 MLP on packed bf16 features")
+    if (cap != ml.capacity or tuple(ml.ray_c.shape) != (cap,) or ml.sh_rec.dim() != 2 or ml.sh_rec.shape[1] != 40
+            or ml.total.dtype != torch.int32 or ml.total.numel() != 1):
+        raise ValueError("march: ray index / SH records / total of the request do not match the points")
+    raw = torch.empty(cap, 4, device=dev, dtype=torch.float32)
+    if cap == 0:
+        return raw
+    sh_rec, n_rec = _lib.ptr(ml.sh_rec, "sh_rec"), ml.sh_rec.shape[0]
+    total = _lib.ptr(ml.total, "total", torch.int32)
+    pts = inputs.detach().float().contiguous()
+    weights = _weights_struct(fn.mlp_weights())
+    m = min(cap, ml.max_points)
+    feat, keep = torch.empty(L, m, device=dev, dtype=torch.int32), torch.empty(m, device=dev, dtype=torch.bool)
+    for s0 in range(0, cap, m):
+        k = min(m, cap - s0)
+        embed_fn.encode_into(pts[s0:s0 + k], feat, 1, m, keep, half=req.half, packed=True, count=(ml.total, s0))
+        _lib.call("nerf_mlp_fwd_bf16_pkbf_rays_dev", _lib.ptr(feat, "feat", torch.int32), 1, m, sh_rec,
+                  _lib.ptr_at(ml.ray_c, s0, "ray_c", torch.int32), n_rec, _lib.ptr(keep, "keep", torch.bool), total, s0,
+                  k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), _lib.stream())
     return raw
 
 

@@ -11,6 +11,10 @@ alternation in the same process, as "fp16:NAME".
 --feature-precision: the packed bf16 launches of both table formats (nerf_hash_encode_fwd_pkbf,
 nerf_hash_encode_fwd_half_pkbf) join the alternation as "fp32:pkbf" and "fp16:pkbf": the ratio of each
 unpacked launch's median to its packed twin's, and whether the words are the rounded features.
+--device-sized: instead of the above, the packed launch on fp32 tables sized on the device
+(nerf_hash_encode_fwd_pkbf_dev) against the host-sized one at the same count n, in the same alternation:
+the default grid at capacity n and 4 n, the grid caps --max-blocks (default 256,512,1024,2048,4096,8192) at capacity n,
+and a launch whose count is 0; medians, ratios to the host-sized launch, and whether the words are the same bits.
 --counter-run: a few launches of each and nothing else, to run under the profiler's counter collection on its own
 (no tracing beside it):  rocprofv3 --pmc TCC_HIT_sum TCC_MISS_sum --output-format csv -d DIR -o t -- \\
     python tools/hash_fwd_ab.py --counter-run
@@ -58,12 +62,16 @@ def main():
     ap.add_argument("--per-round", type=int, default=20)
     ap.add_argument("--variant", action="append", default=[], metavar="NAME=LIB")
     ap.add_argument("--feature-precision", action="store_true")
+    ap.add_argument("--device-sized", action="store_true")
+    ap.add_argument("--max-blocks", default="256,512,1024,2048,4096,8192")
     ap.add_argument("--counter-run", action="store_true")
     ap.add_argument("--counters", default=None)
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     if a.counters:
         report = {"l2_counters": counters(a.counters)}
+    elif a.device_sized:
+        report = run_device_sized(a)
     else:
         report = run(a)
     if a.out:
@@ -189,6 +197,93 @@ def run(a):
             torch.cuda.synchronize()
             ts.append(e0.elapsed_time(e1))
         report["tables_to_half_us_median"] = round(float(np.median(ts)) * 1e3, 1)
+    return report
+
+
+def alternate(fns, rounds, per_round):
+    """run()'s protocol: per round three warm-up launches of each, then per_round timed launches of each in turn
+    -> {name: [ms]}."""
+    import torch
+    ts = {name: [] for name in fns}
+    for _ in range(rounds):
+        for fn in fns.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        for _ in range(per_round):
+            for name, fn in fns.items():
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                ts[name].append(e0.elapsed_time(e1))
+    return ts
+
+
+def ab_row(ts, base="host"):
+    """alternate()'s times as a table row: median and min in us per launch, and each median over `base`'s."""
+    import numpy as np
+    row = {name + "_us_median": round(float(np.median(v)) * 1e3, 1) for name, v in ts.items()}
+    row.update({name + "_us_min": round(float(np.min(v)) * 1e3, 1) for name, v in ts.items()})
+    row.update({f"{name}_over_{base}": round(float(np.median(v) / np.median(ts[base])), 3) for name, v in ts.items()
+                if name != base})
+    return row
+
+
+def run_device_sized(a):
+    import numpy as np
+    import torch
+
+    import indoor_nerf_amd as nerf
+    from indoor_nerf_amd import _lib
+    from tables import blender_bbox
+
+    if not torch.cuda.is_available():
+        raise SystemExit("hash_fwd_ab: needs a GPU (a time measured elsewhere says nothing)")
+    dev = torch.device("cuda:0")
+    lo, hi = blender_bbox()
+    emb = nerf.HashEmbedder((torch.from_numpy(lo), torch.from_numpy(hi)), finest_resolution=1024).to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(0)
+    with torch.no_grad():
+        for e in emb.embeddings:
+            e.weight.copy_((torch.rand(e.weight.shape, device=dev, generator=g) * 2 - 1) * 0.05)
+    meta, L = emb._meta, emb.n_levels
+    tabs = _lib.ptr_array(emb.tables())
+    caps = [int(c) for c in a.max_blocks.split(",")]
+    report = {"device": torch.cuda.get_device_name(0), "n_levels": L, "log2_T": meta["log2_T"], "points": {}}
+    for R, S in SHAPES:
+        n = R * S
+        o = 4.0 * torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        d = torch.nn.functional.normalize(-o + 0.8 * torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        t = torch.linspace(2.0, 6.0, S, device=dev)
+        pts = torch.zeros(4 * n, 3, device=dev)
+        pts[:n] = (o[:, None] + d[:, None] * t[None, :, None]).reshape(-1, 3)
+        total, zero = (torch.tensor([v], device=dev, dtype=torch.int32) for v in (n, 0))
+        words = {k: torch.zeros(L * 4 * n, device=dev, dtype=torch.int32) for k in ("host", "dev")}
+        keep = torch.empty(4 * n, device=dev, dtype=torch.bool)
+        back = lambda k, sl: (_lib.ptr(words[k], dtype=torch.int32), 1, sl, _lib.ptr(keep, dtype=torch.bool), _lib.stream())  # noqa: E731
+        box = (meta["bmin"], meta["bmax"], meta["res"], L, meta["log2_T"], tabs)
+
+        def host():
+            _lib.call("nerf_hash_encode_fwd_pkbf", _lib.ptr(pts), n, *box, *back("host", n))
+
+        def device(cap, max_blocks=0, count=total):
+            _lib.call("nerf_hash_encode_fwd_pkbf_dev", _lib.ptr(pts), _lib.ptr(count, dtype=torch.int32), 0, cap,
+                      max_blocks, *box, *back("dev", cap))
+
+        fns = {"host": host, "host again": host, "dev capacity n": lambda: device(n),
+               "dev capacity 4n": lambda: device(4 * n), "dev empty, capacity n": lambda: device(n, 0, zero)}
+        for c in caps:
+            fns[f"dev capacity n, max_blocks {c}"] = (lambda c=c: device(n, c))
+        host()
+        device(n)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(words["host"][:L * n], words["dev"][:L * n]))
+        row = ab_row(alternate(fns, a.rounds, a.per_round))
+        row["dev_words_are_the_host_words"] = same
+        report["points"][str(n)] = row
+        del words, pts, keep
     return report
 
 

@@ -18,7 +18,11 @@ collection on its own. --out FILE also writes the JSON.
 --march-sh: only the A/B of the three forwards on per-point SH rows (nerf_mlp_fwd_ord, nerf_mlp_fwd_bf16,
 nerf_mlp_fwd_bf16_pkbf at sh_stride 16) against the same forwards reading one SH record per ray through a ray index
 (nerf_mlp_fwd_rays, nerf_mlp_fwd_bf16_rays, nerf_mlp_fwd_bf16_pkbf_rays), segments of 49 consecutive
-points per ray, at the same two point counts and cache states as --feature-precision. --counter-run applies."""
+points per ray, at the same two point counts and cache states as --feature-precision. --counter-run applies.
+
+--device-sized: only the A/B of nerf_mlp_fwd_bf16_pkbf_rays against nerf_mlp_fwd_bf16_pkbf_rays_dev,
+which reads its point count on the device: count n in a capacity of n and of 4 n, and a count of 0, at 262,144,
+786,432 and 6,291,456 points, features hot."""
 import argparse
 import ctypes
 import json
@@ -253,17 +257,81 @@ def march_sh_ab(dev, counter_run=False, rounds=5, per_round=20, segment=49):
     return out
 
 
+def device_sized_ab(dev, rounds=5, per_round=20, segment=49):
+    """The --device-sized table: nerf_mlp_fwd_bf16_pkbf_rays at n points against
+    nerf_mlp_fwd_bf16_pkbf_rays_dev at count n in a capacity of n and of 4 n, and a launch whose count is 0, at 262,144,
+    786,432 and 6,291,456 points (features hot), alternating after a warm-up; host-sized twice (the run's spread)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from hash_fwd_ab import ab_row, alternate      # the alternation protocol and the row, shared with that tool
+    from tables import blender_bbox
+    lo, hi = blender_bbox()
+    emb = nerf.HashEmbedder((torch.from_numpy(lo), torch.from_numpy(hi)), finest_resolution=1024).to(dev).eval()
+    g = torch.Generator(device=dev).manual_seed(0)
+    net = nerf.NeRFSmall(2, 64, 15, 3, 64, 32, 16).to(dev)
+    w = _lib.MlpWeights(*[_lib.ptr(p.detach()).value for p in net.mlp_weights()])
+    with torch.no_grad():
+        for e in emb.embeddings:
+            e.weight.copy_((torch.rand(e.weight.shape, device=dev, generator=g) * 2 - 1) * 0.05)
+    L = emb.n_levels
+    out = {}
+    for R, S in ((4096, 64), (4096, 192), (32768, 192)):
+        n = R * S
+        o = 4.0 * torch.nn.functional.normalize(torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        d = torch.nn.functional.normalize(-o + 0.8 * torch.randn(R, 3, device=dev, generator=g), dim=-1)
+        t = torch.linspace(2.0, 6.0, S, device=dev)
+        pts = (o[:, None] + d[:, None] * t[None, :, None]).reshape(-1, 3).contiguous()
+        n_rays = -(-n // segment)
+        ray_of = torch.zeros(4 * n, device=dev, dtype=torch.int32)
+        ray_of[:n] = (torch.arange(n, device=dev) // segment).to(torch.int32)
+        views = torch.nn.functional.normalize(torch.randn(n_rays, 3, device=dev, generator=g), dim=-1)
+        rays = torch.cat([torch.zeros(n_rays, 8, device=dev), views], 1).contiguous()
+        rec = torch.empty(n_rays, 40, device=dev)
+        _lib.call("nerf_ray_sh_records", _lib.ptr(rays), n_rays, 11, _lib.ptr(rec), _lib.stream())
+        words = {c: torch.zeros(L, c, device=dev, dtype=torch.int32) for c in (n, 4 * n)}
+        keep = torch.ones(4 * n, device=dev, dtype=torch.bool)
+        with torch.no_grad():
+            emb.encode_into(pts, words[n], 1, n, keep, packed=True)
+        words[4 * n][:, :n] = words[n]
+        total, zero = (torch.tensor([v], device=dev, dtype=torch.int32) for v in (n, 0))
+        raws = {k: torch.zeros(4 * n, 4, device=dev) for k in ("host", "dev")}
+        kp, wp, rp = _lib.ptr(keep, dtype=torch.bool), ctypes.byref(w), _lib.ptr(ray_of, dtype=torch.int32)
+
+        def host():
+            _lib.call("nerf_mlp_fwd_bf16_pkbf_rays", _lib.ptr(words[n], dtype=torch.int32), 1, n, _lib.ptr(rec), rp, n_rays,
+                      kp, n, wp, _lib.ptr(raws["host"]), _lib.stream())
+
+        def device(cap, count=total):
+            _lib.call("nerf_mlp_fwd_bf16_pkbf_rays_dev", _lib.ptr(words[cap], dtype=torch.int32), 1, cap, _lib.ptr(rec), rp,
+                      n_rays, kp, _lib.ptr(count, dtype=torch.int32), 0, cap, wp, _lib.ptr(raws["dev"]), _lib.stream())
+
+        fns = {"host": host, "host again": host, "dev capacity n": lambda: device(n),
+               "dev capacity 4n": lambda: device(4 * n), "dev empty, capacity n": lambda: device(n, zero)}
+        host()
+        device(4 * n)
+        torch.cuda.synchronize()
+        same = bool(torch.equal(raws["host"][:n].view(torch.int32), raws["dev"][:n].view(torch.int32)))
+        row = ab_row(alternate(fns, rounds, per_round))
+        row["dev_raw_same_bits"] = same
+        out[str(n)] = row
+        del words, raws
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--device-sized", action="store_true")
     ap.add_argument("--march-sh", action="store_true")
     ap.add_argument("--feature-precision", action="store_true")
     ap.add_argument("--counter-run", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
-    if a.feature_precision or a.march_sh:
+    if a.feature_precision or a.march_sh or a.device_sized:
         report = {"device": torch.cuda.get_device_name(0)}
-        if a.march_sh:
+        if a.device_sized:
+            report["device_sized_ab"] = device_sized_ab(dev)
+        elif a.march_sh:
             report["march_sh_ab"] = march_sh_ab(dev, a.counter_run)
         else:
             report["packed_ab"] = packed_ab(dev, a.counter_run)

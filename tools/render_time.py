@@ -61,6 +61,14 @@ and with the keyword, on fp32 and on fp16 tables. Per variant: the frame time an
 whether the image has the twin's bits, and from one extra frame with a pair of device events around every launch the
 sums of the hash-encoding and of the MLP forward launches.
 
+With --march-sizes the same frame, process and method time device-sized launches instead (render(march=grid,
+march_sizes="device")): through both grids at 192 and 512 lattice samples, in the configuration the
+keyword needs (march_sh="rays", mlp_precision="bf16", feature_precision="bf16"), the plain march and march_stop in
+{1e-2, 1e-3} x march_stop_slab in {32, 64, 128}, each host-sized and device-sized. Per variant: the frame time, its ratio
+to the host-sized twin's and (march_stop rows) to the plain march of the same sizing, the time per extra slab, whether
+the image has the twin's bits; the plain host-sized rows are timed twice, which gives the run's spread. For the K = 192
+plain rows and their (1e-3, slab 32) rows also the launches of a frame, counted and timed.
+
 usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--out bench_out/render_time.json]
        python tools/render_time.py --early-stop [--out profiles/early_stop_render_time.json]
        python tools/render_time.py --ray-bounds [--out profiles/ray_bounds_render_time.json]
@@ -69,6 +77,10 @@ usage: python tools/render_time.py [--frames 10] [--iters 300] [--size 800] [--o
        python tools/render_time.py --table-precision [--out profiles/table_fp16_render_time.json]
        python tools/render_time.py --march-stop [--iters 300 | --opaque-curve 300,1000,2000,4000]
                                                 [--out profiles/march_stop_render_time.json]
+       python tools/render_time.py --march-sizes --iters 1000 [--out profiles/march_sizes_render_time.json]
+       rocprofv3 --kernel-trace --stats --output-format csv -d DIR -o t -- \
+           python tools/render_time.py --march-sizes --trace-sizes host|device --iters 100 --frames 5
+       python tools/render_time.py --trace-summary HOST_CSV DEVICE_CSV --frames 5 [--out profiles/march_sizes_trace.json]
 """
 import argparse
 import json
@@ -495,6 +507,108 @@ def main_march_sh(a):
     write(a, s, report, grid_occupied_fraction={k: g.occupied_fraction() for k, g in grids.items()})
 
 
+def main_march_sizes(a):
+    """The march_sizes table: the march at K = 192 and 512 through both grids in the configuration the
+    keyword needs (SH by ray, bf16 MLP, packed bf16 features), plain and with march_stop 1e-2 and 1e-3 in slabs of 32,
+    64 and 128, each host-sized and device-sized; the pair must give the same image bit for bit. The plain host-sized
+    rows are also timed a second time as variants of their own ("again"): the run's spread."""
+    s = setup(a)
+    fast = dict(march_sh="rays", mlp_precision="bf16", feature_precision="bf16")
+    if a.trace_sizes:       # for a kernel trace of its own: frames of one variant and nothing else after the set-up
+        over = dict(march=s.new_grid("geometry"), march_samples=192, march_stop=1e-3, march_stop_slab=32, **fast,
+                    **({"march_sizes": "device"} if a.trace_sizes == "device" else {}))
+        for _ in range(3 + a.frames):
+            s.timed(over)
+        return
+    grids = {f"{kind} grid": s.new_grid(kind) for kind in ("geometry", "default")}
+    variants, twin, desc = [("dense", {})], {}, {"dense": {}}
+    for gname, grid in grids.items():
+        for K in (192, 512):
+            rows = [(f"{gname}: march, K = {K}", dict(march=grid, march_samples=K, **fast), None, None)]
+            for eps in (1e-2, 1e-3):
+                for slab in (32, 64, 128):
+                    rows.append((f"{rows[0][0]}, stop {eps:g}, slab {slab}",
+                                 dict(rows[0][1], march_stop=eps, march_stop_slab=slab), eps, slab))
+            for base, over, eps, slab in rows:
+                variants += [(base, over), (base + ", device sizes", dict(over, march_sizes="device"))]
+                twin[base + ", device sizes"] = base
+                for name in (base, base + ", device sizes"):
+                    desc[name] = dict(grid=gname, march_samples=K, march_stop=eps, march_stop_slab=slab,
+                                      slabs=1 if slab is None else -(-K // slab), plain=rows[0][0])
+            variants.append((rows[0][0] + ", again", rows[0][1]))
+            twin[rows[0][0] + ", again"] = rows[0][0]
+            desc[rows[0][0] + ", again"] = desc[rows[0][0]]
+
+    report, images = {}, {}
+    for name, over in variants:         # one untimed frame per variant: PSNR, evaluated points, the bits
+        out = s.frame(over)
+        images[name] = out[0]
+        report[name] = dict({k: v for k, v in desc[name].items() if k != "plain"},
+                            march_sizes=over.get("march_sizes", "host"), psnr_db=s.psnr(out[0]))
+        if "march" in over:
+            report[name]["evaluated_points"] = int(out[3]["march_samples"].sum())
+        if name in twin:
+            report[name]["same_bits_as_host_twin"] = bool(torch.equal(images[name].contiguous().view(torch.int32),
+                                                                      images[twin[name]].contiguous().view(torch.int32)))
+    for name, over in variants:         # where the launches' time goes: the K = 192 rows at slab 32 and the plain ones
+        if "march" in over and over["march_samples"] == 192 and over.get("march_stop_slab") in (None, 32) \
+                and over.get("march_stop") in (None, 1e-3) and not name.endswith("again"):
+            ms = launch_times(s, over)
+            report[name].update(all_launches_ms=sum(ms.values()), launches=launch_counts(s, over),
+                                launch_ms={k: round(v, 4) for k, v in sorted(ms.items(), key=lambda kv: -kv[1])})
+    times = measure(a, s, variants, report)
+    for name, base in twin.items():
+        report[name]["time_over_host_twin"] = float(np.median(times[name]) / np.median(times[base]))
+    for name in report:
+        if desc[name].get("march_stop") is not None:
+            sized = ", device sizes" if name.endswith(", device sizes") else ""
+            plain = desc[name]["plain"] + sized
+            report[name]["time_over_plain_march"] = float(np.median(times[name]) / np.median(times[plain]))
+            report[name]["ms_per_extra_slab_vs_plain_march"] = float(
+                (np.median(times[name]) - np.median(times[plain])) / max(1, desc[name]["slabs"] - 1))
+    write(a, s, report, grid_occupied_fraction={k: g.occupied_fraction() for k, g in grids.items()})
+
+
+def trace_summary(path, frames, counts_per_frame):
+    """A kernel trace (rocprofv3 --kernel-trace, csv) of a --trace-sizes run -> per frame of its last `frames` frames:
+    kernels, their summed duration, the span from the first to the last of them, and the idle share of the span. A
+    frame is counts_per_frame launches of march_count_kernel (chunks x slabs)."""
+    import csv
+    rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(path))]
+    rows.sort()
+    starts = [i for i, r in enumerate(rows) if "march_count_kernel" in r[2]]
+    first = starts[-frames * counts_per_frame]
+    part = rows[first:]
+    busy, span = sum(e - b for b, e, _ in part), max(e for _, e, _ in part) - part[0][0]
+    by = {}
+    for b, e, k in part:
+        k = k.split("(")[0].replace("void ", "").replace("nerf::", "")
+        by.setdefault(k, [0, 0.0])
+        by[k][0] += 1
+        by[k][1] += (e - b) / 1e3
+    return {"frames": frames, "kernels_per_frame": len(part) / frames, "kernel_us_per_frame": busy / 1e3 / frames,
+            "span_us_per_frame": span / 1e3 / frames, "idle_share_of_span": 1.0 - busy / span,
+            "mean_gap_us": (span - busy) / 1e3 / max(1, len(part) - 1),
+            "by_kernel_per_frame": {k: {"launches": v[0] / frames, "us": round(v[1] / frames, 1)}
+                                    for k, v in sorted(by.items(), key=lambda kv: -kv[1][1])}}
+
+
+def launch_counts(s, over):
+    """The number of launches of one frame, by entry."""
+    from indoor_nerf_amd import _lib
+    names, call = {}, _lib.call
+
+    def counting(name, *args):
+        names[name] = names.get(name, 0) + 1
+        return call(name, *args)
+    _lib.call = counting
+    try:
+        s.frame(over)
+    finally:
+        _lib.call = call
+    return names
+
+
 def opaque_setup(a, counts):
     """The scene trained afresh at each of `counts` in turn until the dense PSNR of the frame stops rising:
     (setup() of the chosen count, {count: dense PSNR})."""
@@ -582,10 +696,26 @@ def main():
     ap.add_argument("--march-stop", action="store_true", help="time stopping rays inside the march (DESIGN.md §19)")
     ap.add_argument("--feature-precision", action="store_true", help="time packed bf16 features (DESIGN.md §20)")
     ap.add_argument("--march-sh", action="store_true", help="time SH read through a ray index (DESIGN.md §21)")
+    ap.add_argument("--march-sizes", action="store_true", help="time device-sized launches (DESIGN.md §23)")
+    ap.add_argument("--trace-sizes", choices=("host", "device"), default=None,
+                    help="--march-sizes: only 3 + --frames frames of the geometry grid's K = 192, stop 1e-3, slab 32 row "
+                         "with that sizing, to run under a kernel trace")
     ap.add_argument("--opaque-curve", default=None,
                     help="--march-stop: training iteration counts to try in turn until the dense PSNR stops rising")
+    ap.add_argument("--trace-summary", nargs=2, metavar=("HOST_CSV", "DEVICE_CSV"), default=None,
+                    help="summarise the kernel traces of the two --trace-sizes runs (no GPU needed)")
     a = ap.parse_args()
-    mode, out = ((main_march_sh, "profiles/march_sh_render_time.json") if a.march_sh else
+    if a.trace_summary:
+        chunks = -(-a.size * a.size // a.chunk)
+        out = {m: trace_summary(p, a.frames, chunks * 6) for m, p in zip(("host", "device"), a.trace_summary)}
+        out["variant"] = "geometry grid: march, K = 192, stop 1e-3, slab 32 (6 slabs), SH by ray, bf16 MLP, bf16 features"
+        if a.out:
+            with open(a.out, "w") as fp:
+                json.dump(out, fp, indent=1)
+        print(json.dumps(out))
+        return
+    mode, out = ((main_march_sizes, "profiles/march_sizes_render_time.json") if a.march_sizes else
+                 (main_march_sh, "profiles/march_sh_render_time.json") if a.march_sh else
                  (main_feature_precision, "profiles/feat_bf16_render_time.json") if a.feature_precision else
                  (main_march_stop, "profiles/march_stop_render_time.json") if a.march_stop else
                  (main_table_precision, "profiles/table_fp16_render_time.json") if a.table_precision else
