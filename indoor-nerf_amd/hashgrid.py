@@ -193,7 +193,8 @@ _RETIRED = []
 def bwd_workspace(n_levels, log2_T, n_points, device):
     """Device workspace of nerf_hash_encode_bwd_ws (the binned backward's per-chunk regions), one per
     device, grown to the largest (n_levels, n_points) seen; calls that share it run in stream order
-    (autograd's backward stream). None when the binned path does not apply (log2_T > 19)."""
+    (autograd's backward stream). None when the binned path does not apply: log2_T > 20 (128 owner slices of 2^13
+    rows); the deterministic mode's slices hold 2^12 rows, so it ends at log2_T 19 and raises beyond."""
     det = int(_DET["on"])
     need = int(_lib.load().nerf_hash_encode_bwd_workspace_bytes(n_levels, log2_T, n_points, det))
     if need == 0:

@@ -16,6 +16,7 @@ import numpy as np
 import pytest
 import torch
 
+from hash_bwd_ref import scatter_ref
 from tables import blender_bbox, closed_form_table, synthetic_rays
 
 pytestmark = pytest.mark.gpu
@@ -60,17 +61,7 @@ def test_hash_bwd_deterministic_bitwise_and_accurate(nerf, gpu, oracle):
     xc = torch.from_numpy(x)
     bmin, bmax = torch.from_numpy(lo), torch.from_numpy(hi)
     for lvl in (0, 7, 15):
-        vmin, vmax, idx, _ = oracle.voxel_corners(xc, bmin, bmax, torch.tensor(emb.level_res[lvl]), 19)
-        w = ((xc - vmin) / (vmax - vmin)).double()
-        wx, wy, wz = w[:, 0:1], w[:, 1:2], w[:, 2:3]
-        gl = torch.from_numpy(dfeat[lvl]).double()
-        contrib = []
-        for c in range(8):
-            i, j, k = (c >> 2) & 1, (c >> 1) & 1, c & 1
-            contrib.append(gl * ((wz if k else 1 - wz) * (wy if j else 1 - wy) * (wx if i else 1 - wx)))
-        contrib = torch.stack(contrib, 1).reshape(-1, 2)
-        ref = torch.zeros(1 << 19, 2, dtype=torch.float64).index_add_(0, idx.reshape(-1), contrib)
-        scale = torch.zeros(1 << 19, 2, dtype=torch.float64).index_add_(0, idx.reshape(-1), contrib.abs())
+        ref, scale, _, _ = scatter_ref(oracle, xc, dfeat[lvl], bmin, bmax, emb.level_res[lvl], 19)
         for name, got in (("deterministic", a), ("default", plain)):
             err = (got[lvl].cpu().double() - ref).abs()
             bad = err > 2e-6 * scale + 1e-30

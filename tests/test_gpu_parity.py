@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 import torch
 
+from hash_bwd_ref import edge_points, scatter_ref
 from tables import blender_bbox, closed_form_table, synthetic_rays
 
 pytestmark = pytest.mark.gpu
@@ -93,30 +94,7 @@ def test_hash_encode_edge_points_vs_c_oracle(nerf, gpu):
     from test_abi import _c_hash
     table = closed_form_table()
     emb = _embedder(nerf, gpu, 1024, table)
-    lo, hi = blender_bbox()
-    rng = np.random.RandomState(11)
-    n = 1 << 20
-    x = (lo - 0.3 + (hi - lo + 0.6) * rng.rand(n, 3)).astype(np.float32)
-    res = np.asarray(emb.level_res, np.float32)
-    cell = ((hi.astype(np.float32) - lo.astype(np.float32))[None, :] / res[:, None]).astype(np.float32)   # [L, 3]
-    # grid vertices: base * cell + lo in fp32 (the kernels' vmin), every level, random axes
-    m = n // 4
-    lv = rng.randint(0, len(res), m)
-    k = np.floor(rng.rand(m, 3) * res[lv][:, None]).astype(np.float32)
-    verts = (k * cell[lv] + lo.astype(np.float32)).astype(np.float32)
-    axes = rng.rand(m, 3) < 0.6
-    x[:m][axes] = verts[axes]
-    specials = np.array([0.0, -0.0, 1e-30, -1e-30, 1e-40, 1e-45, 3e-22, 1e30, -1e30, 1e-6, -1e-6],
-                        np.float32)
-    sel = rng.rand(n, 3) < 0.002                                   # scattered: one wave in ~10
-    x[sel] = rng.choice(specials, int(sel.sum()))
-    for a in range(3):                                             # exact box bounds
-        b = rng.rand(n) < 0.01
-        x[b, a] = np.where(rng.rand(int(b.sum())) < 0.5, lo[a], hi[a]).astype(np.float32)
-    x[n - 4096:n - 2048, 1] = 0.0                                   # a run of zero coordinates
-    x[n - 2048:, 2] = 1e-38
-    perm = rng.permutation(n - 4096)
-    x[:n - 4096] = x[perm]
+    x = edge_points(emb.level_res)
     with torch.no_grad():
         feat, keep = emb(torch.from_numpy(x).to(gpu))
     ref, ref_keep, *_ = _c_hash(x, emb.level_res, table)
@@ -150,17 +128,7 @@ def test_hash_encode_small_tables_vs_oracle(nerf, gpu, oracle, log2_T):
     dfeat = torch.from_numpy(rng.randn(65536, 32).astype(np.float32))
     (feat * dfeat.to(gpu)).sum().backward()
     for lvl in (0, 3, 9, 15):
-        vmin, vmax, idx, _ = oracle.voxel_corners(xt, bmin, bmax, res[lvl], log2_T)
-        w = ((xt - vmin) / (vmax - vmin)).double()
-        wx, wy, wz = w[:, 0:1], w[:, 1:2], w[:, 2:3]
-        gl = dfeat[:, 2 * lvl:2 * lvl + 2].double()
-        contrib = []
-        for c in range(8):
-            i, j, k = (c >> 2) & 1, (c >> 1) & 1, c & 1
-            contrib.append(gl * ((wz if k else 1 - wz) * (wy if j else 1 - wy) * (wx if i else 1 - wx)))
-        contrib = torch.stack(contrib, 1).reshape(-1, 2)
-        want = torch.zeros(1 << log2_T, 2, dtype=torch.float64).index_add_(0, idx.reshape(-1), contrib)
-        scale = torch.zeros(1 << log2_T, 2, dtype=torch.float64).index_add_(0, idx.reshape(-1), contrib.abs())
+        want, scale, _, _ = scatter_ref(oracle, xt, dfeat[:, 2 * lvl:2 * lvl + 2], bmin, bmax, res[lvl], log2_T)
         got = emb.embeddings[lvl].weight.grad.cpu().double()
         bad = (got - want).abs() > 2e-6 * scale + 1e-30
         assert not bool(bad.any()), f"level {lvl}: {int(bad.sum())} rows off"
