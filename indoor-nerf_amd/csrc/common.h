@@ -108,9 +108,7 @@ __device__ __forceinline__ float dpp_move(float v) {
 
 // Segmented inclusive wave64 sums of N values per lane, runs = lanes [start, lane] (start: first lane
 // of the lane's run). Intra-row Hillis-Steele (row_shr 1,2,4,8) then the row_bcast 15 / 31 carries
-// of the classic DPP scan, each applied only where the source lane lies in the same run. STEPS: the
-// intra-row distances 1 .. 2^(STEPS-1) are applied (enough when every run is shorter than 2^STEPS
-// lanes); CROSS: the carries across rows.
+// of the classic DPP scan, each applied only where the source lane lies in the same run.
 // Step-major: each step runs over all N values before the next, so a DPP read never follows the
 // VALU write of its source register within the 2-wait-state hazard window (value-major order put
 // an s_nop in front of nearly every DPP step).
@@ -127,37 +125,45 @@ __device__ __forceinline__ void seg_scan_step(float (&v)[N], bool take) {
     }
 #pragma unroll
     for (int i = 0; i < N; ++i) v[i] = take ? t[i] : v[i];   // a select, not a branch
+    // The selected values are pinned here (no instruction): behind a wave-uniform branch the
+    // optimiser otherwise sinks the selects to the join and carries t across it, which costs one
+    // v_mov per value and step.
+#pragma unroll
+    for (int i = 0; i < N; ++i) asm volatile("" : "+v"(v[i]));
 }
 
-template <int N, int STEPS, bool CROSS>
-__device__ __forceinline__ void wave_segmented_scan_steps(float (&v)[N], int lane, int start) {
-    const int r16 = lane & 15, row = lane >> 4, span = lane - start;
-    const bool t1 = r16 >= 1 && span >= 1;
-    const bool t2 = r16 >= 2 && span >= 2;
-    const bool t4 = r16 >= 4 && span >= 4;
-    const bool t8 = r16 >= 8 && span >= 8;
-    const bool tb15 = (row & 1) && start <= 16 * row - 1;
-    const bool tb31 = row >= 2 && start <= 31;
-    seg_scan_step<N, 0x111, 0xF>(v, t1);
-    if constexpr (STEPS >= 2) seg_scan_step<N, 0x112, 0xF>(v, t2);
-    if constexpr (STEPS >= 3) seg_scan_step<N, 0x114, 0xF>(v, t4);
-    if constexpr (STEPS >= 4) seg_scan_step<N, 0x118, 0xF>(v, t8);
-    if constexpr (CROSS) {
-        seg_scan_step<N, 0x142, 0xA>(v, tb15);
-        seg_scan_step<N, 0x143, 0xC>(v, tb31);
-    }
-}
-
-// The full scan, or a shorter one chosen once per wave (ballots): runs of consecutive samples in
-// one voxel are mostly 2-4 lanes long and seldom cross a 16-lane row, so most waves need one or two
-// of the six steps.
+// The scan, with the steps chosen once per wave (ballots; every branch is wave-uniform): runs of
+// consecutive samples in one voxel are mostly 2-8 lanes long, so the longest span of the wave picks
+// how many of the intra-row steps run (a step of distance d changes nothing when every span is
+// below d), and a wave whose runs are all shorter than 17 lanes takes ONE carry step instead of the
+// bcast15 / bcast31 pair: such a run crosses at most one row boundary, so a row-k lane whose run
+// began in row k - 1 adds the inclusive partial of lane 16k - 1 — row_bcast:15 into rows 1, 2 and 3
+// at once (lanes 15, 31 and 47 hold what the pair would have read: lane 31 takes the bcast15 step
+// only in a run that began in row 0, and a row-2 lane of that run spans 17 or more). Its row mask
+// is 0xF, not 0xE: row 0 has no source and never takes the step, and with a full mask the move
+// folds into the add (v_add_f32_dpp, 2 instead of 3 VALU per value).
+// The additions and their order are those of the full six steps, so every sum is the same bit for
+// bit. Almost every wave has a run across one of its three row boundaries, and the full form on
+// all of those was the largest phase of the bin pass.
 template <int N>
 __device__ __forceinline__ void wave_segmented_inclusive_sum(float (&v)[N], int lane, int start) {
-    const int span = lane - start;
-    const bool cross = __ballot(start < (lane & ~15)) != 0ull;   // a run continues across a row boundary
-    if (!cross && __ballot(span >= 2) == 0ull) wave_segmented_scan_steps<N, 1, false>(v, lane, start);
-    else if (!cross && __ballot(span >= 4) == 0ull) wave_segmented_scan_steps<N, 2, false>(v, lane, start);
-    else wave_segmented_scan_steps<N, 4, true>(v, lane, start);
+    const int r16 = lane & 15, row = lane >> 4, span = lane - start;
+    const bool enters = start < (lane & ~15);   // the lane's run continues from the row before
+    const bool any2 = __ballot(span >= 2) != 0ull, any4 = __ballot(span >= 4) != 0ull;
+    const bool any8 = __ballot(span >= 8) != 0ull, any16 = __ballot(span >= 16) != 0ull;
+    const bool cross = __ballot(enters) != 0ull;
+    seg_scan_step<N, 0x111, 0xF>(v, r16 >= 1 && span >= 1);
+    if (any2) seg_scan_step<N, 0x112, 0xF>(v, r16 >= 2 && span >= 2);
+    if (any4) seg_scan_step<N, 0x114, 0xF>(v, r16 >= 4 && span >= 4);
+    if (any8) seg_scan_step<N, 0x118, 0xF>(v, r16 >= 8 && span >= 8);
+    if (cross) {
+        if (any16) {   // a run of 17 lanes or more: the carries of the classic scan
+            seg_scan_step<N, 0x142, 0xA>(v, (row & 1) && enters);
+            seg_scan_step<N, 0x143, 0xC>(v, row >= 2 && start <= 31);
+        } else {
+            seg_scan_step<N, 0x142, 0xF>(v, enters);
+        }
+    }
 }
 
 // Wave64 reductions / scans through DPP-capable shuffles.
