@@ -1082,6 +1082,22 @@ int nerf_mlp_fwd_bf16_pkbf_rays_dev(const uint32_t* d_featw, int64_t feat_stride
                                     const uint8_t* d_keep, const int32_t* d_total, int64_t base, int64_t capacity,
                                     const nerf_mlp_weights* weights, float* d_raw, void* stream);
 
+/* ---- Training through the grid march (csrc/march_bwd.hip) ----
+ * Additive entry (the ABI version stays 12). nerf_packed_composite_bwd: the backward of nerf_march_composite with
+ * respect to d_raw. The inputs are that entry's packed list (d_raw [n_points, 4], d_z, d_dist [n_points],
+ * d_offsets [n_rays + 1], d_rays_d [n_rays, 3]; every segment clamped into the list as there) and the upstream
+ * gradients of its outputs, each of which may be NULL (zero): d_g_rgb [n_rays, 3], d_g_disp, d_g_acc, d_g_depth
+ * [n_rays] and d_g_weights [n_points]. d_graw [n_points, 4] is WRITTEN for every entry that lies in a segment
+ * and nothing else is written (an empty segment writes nothing). The forward values are formed as
+ * nerf_march_composite forms them; the per-sample arithmetic is nerf_composite_bwd's for four channels without
+ * noise, entropy or normals: white_bkgd folds -(g_r + g_g + g_b) into g_acc, depth = N / A, disp through
+ * fmaxf(1e-10, depth), graw[:, 3] = 0 where sigma <= 0. A segment of any length works. No atomics: identical
+ * inputs give identical bits. n_rays = 0 or n_points = 0 launches nothing and accepts NULL buffers. */
+int nerf_packed_composite_bwd(const float* d_raw, const float* d_z, const float* d_dist, const int32_t* d_offsets,
+                              const float* d_rays_d, int64_t n_rays, int64_t n_points, int white_bkgd,
+                              const float* d_g_rgb, const float* d_g_disp, const float* d_g_acc,
+                              const float* d_g_depth, const float* d_g_weights, float* d_graw, void* stream);
+
 /* Debug: the bf16 weight image that every block of the fp32-accurate MLP kernels builds in its prologue
  * (csrc/field_x6.hip), copied out by one block that runs that prologue. d_out receives 3 x 11,136 bf16
  * elements (66,816 B): piece k (k = 0, 1, 2; v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1), round to

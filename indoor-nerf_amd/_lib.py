@@ -289,6 +289,9 @@ SIGNATURES = {
                                            c_vp, c_i64, c_i64, c_vp, c_vp],
     "nerf_mlp_fwd_bf16_pkbf_rays_dev": [c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_i64, c_i64,
                                         ctypes.POINTER(MlpWeights), c_vp, c_vp],
+    # training through the grid march: the backward of nerf_march_composite
+    "nerf_packed_composite_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                  c_vp, c_vp],
     # debug: the MLP kernels' prologue image (csrc/field_x6.hip fill_images), 3 x 11,136 bf16 elements
     "nerf_mlp_weight_image": [ctypes.POINTER(MlpWeights), c_vp, c_vp],
 }

@@ -287,8 +287,60 @@ class FieldFn(torch.autograd.Function):
         return (None,) * (7 + n_tab + len(weights)) + tuple(head_grads)
 
 
+class PackedFieldFn(torch.autograd.Function):
+    """The fused field on one slice of a grid march's packed list under gradients (march_grad):
+    pts [n, 3], sh [n, 16] (the points' SH4 rows, as nerf_march_write leaves them) -> raw [n, 4]. The training
+    forward in the identity order with SH rows at stride 16; the backward is a _FieldJob in the third view mode
+    (per-point SH rows), queued with the pass's other field backwards. No reuse, no normals head, no quantizers
+    (occupancy._check_modules and the raw_channels check of the field call)."""
+
+    @staticmethod
+    def forward(ctx, pts, sh, embedder, net, *params):
+        if pts.requires_grad or sh.requires_grad:
+            raise NotImplementedError("run_network: gradients w.r.t. positions/directions are not implemented")
+        n_tab = embedder.n_levels
+        weights = params[n_tab:n_tab + 5]
+        pts, sh = pts.contiguous(), sh.contiguous()
+        P, dev = pts.shape[0], pts.device
+        feat, keep = level_features(n_tab, P, dev), torch.empty(P, device=dev, dtype=torch.bool)
+        raw = torch.empty(P, 4, device=dev, dtype=torch.float32)
+        h3 = None
+        if P > 0:
+            embedder.encode_into(pts, feat, 2, 2 * P, keep)
+            if _SAVE_H3["on"] and not _ACTIVE["on"] and any(ctx.needs_input_grad[4:4 + n_tab + 5]):
+                h3 = torch.empty(int(_lib.load().nerf_mlp_h3_bytes(P)) // 4, device=dev, dtype=torch.float32)
+            _lib.call("nerf_mlp_fwd_h3", _lib.ptr(feat, "feat"), 2, 2 * P, _lib.ptr(sh, "sh_c"), 16, None, 1,
+                      _lib.ptr(keep, "keep", dtype=torch.bool), P, _weights_struct(weights), _lib.ptr(raw, "raw"),
+                      None, None, None, 0, None, _lib.ptr(h3, "h3", allow_none=True), _lib.stream())
+        ctx.save_for_backward(pts, sh, feat, keep, *params)
+        ctx.h3, ctx.spr, ctx.embedder, ctx.n_tab = h3, 1, embedder, n_tab
+        ctx.sh_rays = ctx.reuse = ctx.order = None
+        ctx.frow0 = 0
+        return raw
+
+    @staticmethod
+    def backward(ctx, g_raw):
+        pts, sh, feat, keep, *params = ctx.saved_tensors
+        n_tab = ctx.n_tab
+        tables, weights = params[:n_tab], params[n_tab:n_tab + 5]
+        need_tab = any(t.requires_grad for t in tables)
+        need_w = any(w.requires_grad for w in weights)
+        if pts.shape[0] > 0 and (need_w or need_tab):
+            job = _FieldJob(pts, None, feat, keep, (), None, None, weights, tables, g_raw.contiguous(), None, ctx,
+                            need_w, need_tab)
+            job.sh_points = sh
+            if torch._C._current_graph_task_id() != -1:
+                _pending_field(pts.device).add(job)   # launched with the pass's other field backwards
+            else:
+                _run_field_jobs([job])
+        return (None,) * (4 + len(params))
+
+
 class _FieldJob:
-    """Everything one FieldFn backward needs after its autograd node has returned."""
+    """Everything one FieldFn (or PackedFieldFn) backward needs after its autograd node has returned."""
+
+    sh_points = None     # PackedFieldFn: the points' SH4 rows [P, 16] (sh_stride 16)
+
 
     def __init__(self, pts, viewdirs, feat, keep, head, w0q, arec, weights, tables, g, dgeo, ctx, need_w, need_tab):
         self.pts, self.viewdirs, self.feat, self.keep, self.head = pts, viewdirs, feat, keep, head
@@ -312,7 +364,9 @@ class _FieldJob:
         j.dfeat_stride_point, j.dfeat_stride_level = 2, 2 * P
         if self.order is not None:
             j.order = _point_order(self.order)
-        if self.sh_rays is not None:   # per-ray SH rows (sh_stride 0)
+        if self.sh_points is not None:   # per-point SH rows (sh_stride 16): a march's packed list
+            j.sh, j.sh_stride, j.viewdirs = _lib.ptr(self.sh_points, "sh_c"), 16, None
+        elif self.sh_rays is not None:   # per-ray SH rows (sh_stride 0)
             j.sh, j.sh_stride, j.viewdirs = _lib.ptr(self.sh_rays, "sh_rows"), 0, None
         else:
             j.viewdirs = _lib.ptr(self.viewdirs, "viewdirs")

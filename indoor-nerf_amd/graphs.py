@@ -226,6 +226,9 @@ class GraphedTrainStep:
     def __init__(self, batch_rays, target_s, render_kwargs_train, optimizer, args, H=0, W=0, K=None,
                  grad_hook=None, loss_scale_sparsity=1.0, tv_generator=None, zero_grad=None, warmup=2,
                  post_hook=None, sampler=None):
+        if render_kwargs_train.get("march") is not None and render_kwargs_train.get("march_grad") is True:
+            raise ValueError("GraphedTrainStep: march_grad cannot be captured (the list length of a grid march is read "
+                             "on the host; use train_step)")
         self.rays, self.target = batch_rays, target_s
         # sampler (rays.RaySampler): every iteration draws a new batch into batch_rays / target_s first
         # (train()'s no_batching path, run_nerf.py:975-1004), inside the captured step

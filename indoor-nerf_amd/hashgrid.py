@@ -211,6 +211,9 @@ def bwd_workspace(n_levels, log2_T, n_points, device):
     return hit
 
 
+BIN_BATCH_MAX_JOBS = 8   # csrc/hashgrid.hip: the jobs of one nerf_hash_encode_bwd_bin_batch(_tv) launch
+
+
 class _PendingBins:
     """Binned hash backwards of the running autograd pass that await their owner pass (per device).
     The fine and the coarse pass of a training iteration are two HashEncode nodes scattering into
@@ -321,7 +324,9 @@ class _PendingBins:
         common = (meta["bmin"], meta["bmax"], meta["res"], L, log2_T)
         if self.batch is not None:
             key = (id(self.ws), self.cap, det, L, log2_T, id(meta["bmin"]), id(meta["bmax"]), id(meta["res"]))
-            if self.batch and self.batch[0][1] != key:
+            # another workspace or parameters, or a full launch (nerf_hash_encode_bwd_bin_batch takes up to 8 jobs; only
+            # the slices of a long march list, DESIGN.md §24, come to more): launch what is collected, keep collecting
+            if self.batch and (self.batch[0][1] != key or len(self.batch) >= BIN_BATCH_MAX_JOBS):
                 self._drain_batch()
             self.batch.append((job, key, common, det, (xyz, rows, dfeat, dfeat2, rows2)))
             return

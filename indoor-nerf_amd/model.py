@@ -195,8 +195,11 @@ def _forward_backward(batch_rays, target_s, render_kwargs_train, optimizer, args
     tv_acc = tv_accumulator(render_kwargs_train["embed_fn"]) if tv_w > 0 else None
     # a captured step's TV forward runs inside the fine compositing launch (corners drawn after render)
     tv_early = tv_forward_early(render_kwargs_train["embed_fn"], tv_acc) if tv_w > 0 else None
-    rgb, depth, acc, extras = render(H, W, K, chunk=get("chunk"), rays=batch_rays, retraw=True,
-                                     **render_kwargs_train)
+    # training through the grid march (march= with march_grad=True): one pass, no rgb0, no sparsity
+    # terms (train_loss takes them as None), and render refuses retraw with march
+    marched = render_kwargs_train.get("march") is not None and render_kwargs_train.get("march_grad") is True
+    rgb, depth, acc, extras = render(H, W, K, chunk=get("chunk"), rays=batch_rays,
+                                     **({} if marched else dict(retraw=True)), **render_kwargs_train)
     # run_nerf.py:1011-1037 (img2mse x2, sparsity, TV, mse2psnr) fused into one launch (csrc/loss.hip)
     tv = (total_variation_all(render_kwargs_train["embed_fn"], generator=tv_generator, out=tv_acc, early=tv_early)
           if tv_w > 0 else None)

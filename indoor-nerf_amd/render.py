@@ -198,6 +198,44 @@ def run_composite_jobs(jobs):
                   _lib.stream())
 
 
+class MarchCompositeFn(torch.autograd.Function):
+    """The packed compositing of a grid march under gradients (march_grad): raw [n, 4], z [n],
+    dist [n], offsets int32 [R + 1], rays_d [R, 3] -> (rgb_map, depth_map, acc_map). The forward is
+    nerf_march_composite, the launch of the forward-only march; the backward is nerf_packed_composite_bwd, launched
+    at once. Gradients flow to raw only (z, dist and rays_d are not differentiated, as in CompositeFn)."""
+
+    @staticmethod
+    def forward(ctx, raw, z, dist, offsets, rays_d, white_bkgd):
+        if z.requires_grad or dist.requires_grad or rays_d.requires_grad:
+            raise NotImplementedError("march: gradients w.r.t. z_vals / dists / rays_d are not implemented")
+        ctx.set_materialize_grads(False)
+        raw = raw.contiguous()
+        R, n = rays_d.shape[0], raw.shape[0]
+        f = dict(device=raw.device, dtype=torch.float32)
+        rgb, depth, acc = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
+        if R > 0:
+            _lib.call("nerf_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z, "z_c"), _lib.ptr(dist, "dist_c"),
+                      _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n,
+                      int(bool(white_bkgd)), _lib.ptr(rgb, "rgb"), None, _lib.ptr(acc, "acc"), _lib.ptr(depth, "depth"),
+                      None, _lib.stream())
+        ctx.save_for_backward(raw, z, dist, offsets, rays_d)
+        ctx.white = int(bool(white_bkgd))
+        return rgb, depth, acc
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_depth, g_acc):
+        raw, z, dist, offsets, rays_d = ctx.saved_tensors
+        if g_rgb is None and g_depth is None and g_acc is None:
+            return None, None, None, None, None, None
+        gs = [None if g is None else g.contiguous().float() for g in (g_rgb, g_acc, g_depth)]
+        graw = torch.empty_like(raw)   # a march's segments tile its list: every row is written
+        _lib.call("nerf_packed_composite_bwd", _lib.ptr(raw, "raw"), _lib.ptr(z, "z_c"), _lib.ptr(dist, "dist_c"),
+                  _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), rays_d.shape[0], raw.shape[0],
+                  ctx.white, _lib.ptr(gs[0], "g_rgb", allow_none=True), None, _lib.ptr(gs[1], "g_acc", allow_none=True),
+                  _lib.ptr(gs[2], "g_depth", allow_none=True), None, _lib.ptr(graw, "grad_raw"), _lib.stream())
+        return graw, None, None, None, None, None
+
+
 _DEFER = {"on": True, "off_task": None}
 
 
@@ -403,7 +441,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
                 table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None, march_sh=None,
-                march_sizes=None):
+                march_sizes=None, march_grad=False):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -457,12 +495,21 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     launch depends on a count. The result is bit for bit the call without it, in every entry. With retraw the packed
     entries are views of the first n rows, which costs one read after the chunk's last launch. Composes with
     march_stop=, table_precision=, march_points= and render's ray_bounds=. None and "host" are the call without it:
-    the same launches, the same buffers."""
+    the same launches, the same buffers.
+    march_grad (a bool; with march=): True lets the plain march run under gradients, for training
+    through the grid. The field on the list is then field.PackedFieldFn (per slice of march_points points) and the
+    compositing MarchCompositeFn, whose backward is nerf_packed_composite_bwd; the result holds the same entries,
+    rgb_map, depth_map and acc_map bit for bit those of the call under torch.no_grad(), and with retraw the packed raw
+    is attached to the graph. Under torch.no_grad() the call is the march without it: the same launches, the same
+    bits. Does not combine with march_stop= (the slabs' carried state has no backward); march_sh="rays",
+    mlp_precision="bf16", table_precision="fp16", feature_precision="bf16" and march_sizes="device" stay forward-only.
+    False (the default) leaves every call as it is: march= under gradients is refused."""
     # march_sizes is passed only when given: tests/test_field_request.py pins this call's eight positional arguments
     # and empty keywords for a call without it (the same in render())
     opts = sparse_field.field_options("render_rays", march, march_sh, march_stop, march_stop_slab, mlp_precision,
                                       table_precision, feature_precision,
                                       **({} if march_sizes is None else dict(march_sizes=march_sizes)))
+    march_grad = sparse_field.check_march_grad(march_grad, march, opts.stop, "render_rays")
     nets = [network_fn] + ([] if network_fine is None else [network_fine])
     if opts.half:
         sparse_field.check_table_nets(nets, embed_fn)
@@ -473,7 +520,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  device_sizes=sparse_field.device_sized(march_sizes))
+                                  device_sizes=sparse_field.device_sized(march_sizes), march_grad=march_grad)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -589,8 +636,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
 
 
 def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, perturb, raw_noise_std, predict_normals,
-                 occupancy, early_stop):
-    """render_rays' refusals with march= after field_options', all before any launch -> K."""
+                 occupancy, early_stop, march_grad=False):
+    """render_rays' refusals with march= after field_options', all before any launch -> K. march_grad: the call may
+    run under gradients."""
     from .occupancy import OccupancyGrid, _check_modules, check_march_samples
     from .sparse_field import check_forward_only, check_march_points
     if not isinstance(grid, OccupancyGrid):
@@ -600,7 +648,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
     if occupancy is not None or early_stop is not None:
         raise ValueError("render_rays: march does not combine with occupancy= (the march already masks by its grid) "
                          "or early_stop= (rays are not stopped inside a march)")
-    check_forward_only("march", "render_rays", raw_noise_std)
+    check_forward_only("march", "render_rays", raw_noise_std, grad=march_grad)
     if perturb > 0.:
         raise ValueError("render_rays: march needs perturb == 0 (the lattice is the unperturbed coarse sampling)")
     if lindisp:
@@ -614,7 +662,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, opts, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None, device_sizes=False):
+                       predict_normals=False, occupancy=None, early_stop=None, device_sizes=False, march_grad=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing. opts: the call's FieldOptions. With
     opts.stop (march_stop) the same in slabs (_march_slabs). opts.by_ray (march_sh="rays", DESIGN.md
@@ -622,10 +670,13 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     packed rays through it. device_sizes (march_sizes="device", DESIGN.md §23): the list's length stays on the device;
     the list is allocated at its capacity R K, the composite is given that capacity as its list bound (it clamps a
     segment into the list, and every offset is at most the true length, which is at most the capacity) and the field
-    runs whenever the capacity is not 0."""
+    runs whenever the capacity is not 0. march_grad under gradients: the field call's list allows
+    gradients (field.PackedFieldFn), the compositing is MarchCompositeFn, and both run for an empty list too, so that
+    the maps stay attached to the graph."""
     run_fn = network_fn if network_fine is None else network_fine
     K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
-                     predict_normals, occupancy, early_stop)
+                     predict_normals, occupancy, early_stop, march_grad)
+    train = march_grad and torch.is_grad_enabled()   # march_sh="rays" and march_sizes="device" have refused gradients
     if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
         raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
     by_ray = opts.by_ray
@@ -641,7 +692,7 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
             march = sparse_field.MarchList(None, march_points, ray_c=sh_c, sh_rec=records[0], total=total,
                                            capacity=None if total is None else pts_c.shape[0])
         else:
-            march = sparse_field.MarchList(sh_c, march_points)
+            march = sparse_field.MarchList(sh_c, march_points, grad=train)
         return _query(network_query_fn, pts_c, rays[:, 8:11], run_fn, opts.request(march=march))[0]
 
     if opts.stop is not None:
@@ -660,8 +711,13 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     else:
         grid._last = (n, R * K)
         raw = field(rays, pts_c, sh_c) if n > 0 else torch.empty(0, 4, **f)
-    rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
-    if R > 0:
+    if train:
+        if n == 0:
+            raw = field(rays, pts_c, sh_c)
+        rgb_map, depth_map, acc_map = MarchCompositeFn.apply(raw, z_c, dist_c, offsets, rays_d, white_bkgd)
+    else:
+        rgb_map, depth_map, acc_map = torch.empty(R, 3, **f), torch.empty(R, **f), torch.empty(R, **f)
+    if R > 0 and not train:
         _lib.call("nerf_march_composite", _lib.ptr(raw, "raw"), _lib.ptr(z_c, "z_c"), _lib.ptr(dist_c, "dist_c"),
                   _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d"), R, n, int(bool(white_bkgd)),
                   _lib.ptr(rgb_map, "rgb"), None, _lib.ptr(acc_map, "acc"), _lib.ptr(depth_map, "depth"), None,
@@ -913,7 +969,8 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     march, march_samples, march_points go to render_rays; with ray_bounds each ray's lattice
     spans its own [near', far']. mlp_precision and table_precision go to
     render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
-    §20), march_sh and march_sizes (the one count read per frame of ray_bounds stays).
+    §20), march_sh and march_sizes (the one count read per frame of ray_bounds stays),
+    and march_grad (the march under gradients; ray_bounds stays forward-only).
     retraw is refused with march: the packed entries of several chunks do not
     concatenate."""
     # render_rays' value checks, also when no chunk reaches it (ray_bounds with every ray missed)
@@ -923,6 +980,7 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
                                       kwargs.get("table_precision"), kwargs.get("feature_precision"),
                                       **({} if kwargs.get("march_sizes") is None
                                          else dict(march_sizes=kwargs["march_sizes"])))
+    sparse_field.check_march_grad(kwargs.get("march_grad", False), kwargs.get("march"), opts.stop, "render")
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")

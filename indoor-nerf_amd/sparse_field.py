@@ -52,11 +52,14 @@ class MarchList:
     rays, sh_c [n, 16], and the largest slice of points per encode + MLP launch. With march_sh="rays" 
     sh_c is None and the list carries the points' ray index, ray_c int32 [n], and one SH record per ray, sh_rec
     [R, 40] (0 <= ray_c < R: the march's write guarantees it). With march_sizes="device"  the list's
-    buffers hold `capacity` entries and its length is `total`, one int32 element in device memory."""
+    buffers hold `capacity` entries and its length is `total`, one int32 element in device memory. grad (march_grad,
+    DESIGN.md §24): the field call may run under gradients, through field.PackedFieldFn; only a list of SH rows."""
 
     total = capacity = None     # a host-sized list: its length is the tensors'
+    grad = False                # a forward-only list
 
-    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None, total=None, capacity=None):
+    def __init__(self, sh_c, max_points=DEFAULT_MARCH_POINTS, ray_c=None, sh_rec=None, total=None, capacity=None,
+                 grad=False):
         if (sh_c is None) == (ray_c is None) or (ray_c is None) != (sh_rec is None):
             raise ValueError("march: a request carries either sh_c or (ray_c, sh_rec)")
         if (total is None) != (capacity is None) or (total is not None and ray_c is None):
@@ -65,6 +68,10 @@ class MarchList:
         self.ray_c, self.sh_rec = ray_c, sh_rec
         if total is not None:     # a host-sized list stays the four attributes it was
             self.total, self.capacity = total, capacity
+        if grad:                  # likewise: a forward-only list carries nothing new
+            if sh_c is None:
+                raise ValueError("march: a list under gradients carries SH rows (the backward reads per-point SH rows)")
+            self.grad = True
 
 
 class FieldRequest:
@@ -313,26 +320,43 @@ def check_march_sh(value, march, prefix):
     return True
 
 
-def check_forward_only(what, prefix, raw_noise_std=0.):
-    """The refusals every forward-only keyword `what` of `prefix` (render_rays, render) shares: no gradients, no
-    raw noise."""
-    if torch.is_grad_enabled():
+def check_march_grad(value, march, stop, prefix):
+    """march_grad of `prefix` (render_rays, render) -> whether the march may run under gradients; its
+    refusals, one fixed sentence each: a value that is not a bool, True without march=, True with march_stop= (stop:
+    check_march_stop's answer). It follows field_options, whose forward-only keywords refuse gradients first."""
+    if not isinstance(value, bool):
+        raise ValueError(f"{prefix}: march_grad must be a bool, got {value!r}")
+    if not value:
+        return False
+    if march is None:
+        raise ValueError(f"{prefix}: march_grad=True needs march= (the gradients are those of a grid march)")
+    if stop is not None:
+        raise ValueError(f"{prefix}: march_grad=True does not combine with march_stop= (the slabs' carried state has no "
+                         "backward)")
+    return True
+
+
+def check_forward_only(what, prefix, raw_noise_std=0., grad=False):
+    """The refusals every forward-only keyword `what` of `prefix` (render_rays, render) shares: no gradients (grad:
+    the call carries march_grad=True), no raw noise."""
+    if torch.is_grad_enabled() and not grad:
         raise ValueError(f"{prefix}: {what} is forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
     if raw_noise_std > 0.:
         raise ValueError(f"{prefix}: {what} needs raw_noise_std == 0 (noise makes relu(sigma + noise) > 0 at skipped "
                          "samples)")
 
 
-def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embeddirs_fn):
+def _begin_field_call(what, inputs_ok, shape_words, viewdirs, fn, embed_fn, embeddirs_fn, grad=False):
     """What run_network_sparse and run_network_packed do first: their refusals, all before any launch (inputs_ok:
-    the inputs are what shape_words says), then the step count of a training-mode encoder."""
+    the inputs are what shape_words says; grad: the request's list allows gradients, MarchList.grad), then the step
+    count of a training-mode encoder."""
     if not isinstance(embeddirs_fn, SHEncoder) or viewdirs is None or not inputs_ok:
         raise ValueError(f"{what}: needs the fused field call (SHEncoder view encoding, viewdirs, {shape_words})")
     _check_modules(embed_fn, fn, what)
     if fn.raw_channels != 4:
         raise ValueError(f"{what}: a normals head is not supported (run_network's box mask then lands on n_z, "
                          "not on sigma, so a skipped sample is not a zero-weight sample)")
-    if torch.is_grad_enabled():
+    if torch.is_grad_enabled() and not grad:
         raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
     if embed_fn.training:
         embed_fn.current_step += 1
@@ -346,7 +370,10 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
     from .field import _weights_struct
     ml = req.march
     by_ray = ml.ray_c is not None
-    _begin_field_call("march", inputs.dim() == 2, "packed inputs [n, 3]", viewdirs, fn, embed_fn, embeddirs_fn)
+    _begin_field_call("march", inputs.dim() == 2, "packed inputs [n, 3]", viewdirs, fn, embed_fn, embeddirs_fn,
+                      grad=ml.grad)
+    if ml.grad and torch.is_grad_enabled():
+        return _run_network_packed_grad(inputs, fn, embed_fn, req)
     if ml.total is not None:
         return _run_network_packed_dev(inputs, fn, embed_fn, req)
     n, dev, L = inputs.shape[0], inputs.device, embed_fn.n_levels
@@ -371,6 +398,26 @@ def run_network_packed(inputs, viewdirs, fn, embed_fn, embeddirs_fn, req):
                     _lib.ptr(keep, "keep", torch.bool), k, weights, _lib.ptr_at(raw, 4 * s0, "raw"), None,
                     (_lib.ptr_at(ml.ray_c, s0, "ray_c", torch.int32), sh_rec, n_rec) if by_ray else None)
     return raw
+
+
+def _run_network_packed_grad(inputs, fn, embed_fn, req):
+    """run_network_packed under gradients (march_grad): the list in slices of at most max_points points,
+    each its own application of field.PackedFieldFn with its own saved features; the raws are concatenated. An empty
+    list is one application on no points, which launches nothing and keeps raw attached to the graph."""
+    from .field import PackedFieldFn
+    ml = req.march
+    if req.bf16 or req.half or req.packed:
+        what = "table_precision" if req.half else "feature_precision" if req.packed else "mlp_precision"
+        raise ValueError(f"{what}: forward-only (call under torch.no_grad(); {NOT_IN_TRAINING[what]})")
+    n = inputs.shape[0]
+    if tuple(ml.sh_c.shape) != (n, 16):
+        raise ValueError("march: SH rows of the request do not match the points")
+    pts, sh_c = inputs.detach().float().contiguous(), ml.sh_c.detach().float().contiguous()
+    params = (*embed_fn.tables(), *fn.mlp_weights())
+    m = max(1, min(n, ml.max_points))
+    parts = [PackedFieldFn.apply(pts[s0:s0 + m], sh_c[s0:s0 + m], embed_fn, fn, *params)
+             for s0 in range(0, max(n, 1), m)]
+    return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
 
 
 def _run_network_packed_dev(inputs, fn, embed_fn, req):
