@@ -1098,6 +1098,34 @@ int nerf_packed_composite_bwd(const float* d_raw, const float* d_z, const float*
                               const float* d_g_rgb, const float* d_g_disp, const float* d_g_acc,
                               const float* d_g_depth, const float* d_g_weights, float* d_graw, void* stream);
 
+/* ---- A jittered lattice for the grid march (csrc/march.hip) ----
+ * Additive entries (the ABI version stays 12). nerf_march_count and nerf_march_write over the whole lattice with
+ * sample k of ray r at the depth nerf_sample_stratified writes with lindisp = 0, perturb = 1, in every bit. With
+ * b_k = near * (1 - t_k) + far * t_k: lower = k > 0 ? 0.5f * (b_k + b_{k-1}) : b_k, upper = k + 1 < n_samples ?
+ * 0.5f * (b_{k+1} + b_k) : b_k, z_k = lower + (upper - lower) * u. The uniforms have the sampler's precedence:
+ * u = d_u[r * n_samples + k] if d_u ([n_rays, n_samples]) is given; else philox_uniform(seed, offset,
+ * r * n_samples + k) with the pair d_rng[0], d_rng[1] (device memory, 8-B aligned) if d_rng is given, else the
+ * host's (seed, offset). p_k = o + d * z_k is kept by the cell rule, as there. The count and the write of one list
+ * must be given the same uniforms.
+ *
+ * nerf_jitter_march_count: nerf_march_count's arguments, checks and outputs, then the four of the uniforms.
+ * nerf_jitter_march_write: nerf_march_write's arguments and checks, then d_ray_c and the four of the uniforms.
+ *   d_dist_c[idx] = z_{k+1} - z_k of the JITTERED depths (the next lattice sample, kept or not; 1e10f for k =
+ *   n_samples - 1): what compositing computes from the dense jittered z. Exactly one of d_sh_c ([capacity, 16], 16-B
+ *   aligned, rows of 11 columns: the ray's SH4 row per entry, as nerf_march_write) and d_ray_c ([capacity] int32:
+ *   the ray's row number per entry, as nerf_rays_march_write; rows of 8 columns are accepted) must be non-NULL; both
+ *   or neither is refused. n_rays = 0 launches nothing and accepts NULL buffers. */
+int nerf_jitter_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                            const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                            int32_t* d_counts, int32_t* d_offsets, float* d_rays_d, void* d_workspace,
+                            size_t workspace_bytes, const float* d_u, uint64_t seed, uint64_t offset,
+                            const uint64_t* d_rng, void* stream);
+int nerf_jitter_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t, int64_t n_samples,
+                            const float* bbox_min, const float* bbox_max, int res, const uint32_t* d_bits,
+                            const int32_t* d_counts, const int32_t* d_offsets, int64_t n_points, int64_t capacity,
+                            float* d_pts_c, float* d_z_c, float* d_dist_c, float* d_sh_c, int32_t* d_ray_c,
+                            const float* d_u, uint64_t seed, uint64_t offset, const uint64_t* d_rng, void* stream);
+
 /* Debug: the bf16 weight image that every block of the fp32-accurate MLP kernels builds in its prologue
  * (csrc/field_x6.hip), copied out by one block that runs that prologue. d_out receives 3 x 11,136 bf16
  * elements (66,816 B): piece k (k = 0, 1, 2; v0 = bf16(v), v1 = bf16(v - v0), v2 = bf16(v - v0 - v1), round to

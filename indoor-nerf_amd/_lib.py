@@ -292,6 +292,12 @@ SIGNATURES = {
     # training through the grid march: the backward of nerf_march_composite
     "nerf_packed_composite_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
                                   c_vp, c_vp],
+    # a jittered lattice for the grid march: the count's and the write's arguments, then (the write:
+    # d_ray_c and) the sampler's uniforms (d_u, seed, offset, d_rng)
+    "nerf_jitter_march_count": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                ctypes.c_size_t, c_vp, c_u64, c_u64, c_vp, c_vp],
+    "nerf_jitter_march_write": [c_vp, c_i64, c_int, c_vp, c_i64, c_f32p, c_f32p, c_int, c_vp, c_vp, c_vp, c_i64, c_i64,
+                                c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u64, c_u64, c_vp, c_vp],
     # debug: the MLP kernels' prologue image (csrc/field_x6.hip fill_images), 3 x 11,136 bf16 elements
     "nerf_mlp_weight_image": [ctypes.POINTER(MlpWeights), c_vp, c_vp],
 }

@@ -49,6 +49,29 @@
 //     training path and is not touched), and both files are built with -ffp-contract=off, so the bits agree.
 //   nerf_rays_march_write / nerf_rays_slab_march_write: march_write_kernel<true>: the write's walk with
 //     ray_c[idx] = r in place of the SH row; no SH is evaluated and rows of 8 columns are accepted.
+//
+// A jittered lattice: nerf_jitter_march_count / nerf_jitter_march_write walk the whole lattice with
+// sample k of ray r at the depth sampling.hip's sample_stratified_kernel writes with lindisp = 0, perturb = 1 (its
+// lines restated in jitter_depth; that file is on the training path and is not touched; both files are built with
+// -ffp-contract=off, so the bits agree). With b_k = march_depth(t_k):
+//   lower = k > 0 ? 0.5f * (b_k + b_{k-1}) : b_k;   upper = k + 1 < K ? 0.5f * (b_{k+1} + b_k) : b_k;
+//   z_k = lower + (upper - lower) * u,   u = d_u[r K + k], else philox_uniform(seed, offset, r K + k) with the pair
+//   from d_rng if given, else the host's (the sampler's precedence);
+//   p_k = o + d * z_k, kept by the cell rule; dist_k = z_{k+1} - z_k of the JITTERED depths, 1e10f for k = K - 1.
+// These are kernels of their own (jitter_count_kernel, jitter_write_kernel<kRays>) with the jitter's arguments in a
+// second kernel parameter: march_sample, the plain kernels and MarchArgs' layout are as they were, so the unjittered
+// entries keep their code and their bits.
+//   Philox: one philox_uniform per lane and iteration, three of its four outputs unused. A wave pays for a VALU
+//     instruction whether 16 or 64 of its lanes are active, so 16 lanes evaluating philox_uniform4 for the 64 samples
+//     of ONE iteration would issue the same ten rounds and add four cross-lane moves; sharing pays only if one
+//     evaluation serves four iterations (256 samples), which needs the K % 4 != 0 straddle handled per ray (the
+//     groups of four are groups of r K + k, not of k) and a staging buffer. Per lane and iteration the index r K + k
+//     goes straight into philox_uniform, so a group that straddles two rays is simply evaluated by the lanes of both
+//     rays' waves: the bits are philox_uniform(..., r K + k) by construction.
+//   The next sample's depth: the write walks one iteration ahead. Iteration i + 1's depths (its Philox, its cell
+//     tests) are computed before iteration i is stored; lane l < 63 takes z_{k+1} from lane l + 1 (__shfl_down) and
+//     lane 63 from lane 0 of the iteration ahead (a broadcast of that lane, __shfl). Every depth is evaluated exactly once: K per ray and
+//     no 65th per iteration. The count walk needs z_k only.
 #include "compact_common.h"
 #include "occ_common.h"
 
@@ -213,6 +236,108 @@ __global__ void __launch_bounds__(kMarchThreads) march_write_kernel(MarchArgs a)
             }
         }
         base += __popcll(mask);
+    }
+}
+
+// ---------------------------------------------------------------- the jittered lattice
+struct JitterArgs {
+    const float* u;          // optional [R, K]: the uniforms
+    uint64_t seed, offset;   // else Philox with this pair,
+    const uint64_t* rng;     // or with the device pair rng[0], rng[1] if given
+};
+
+// sampling.hip's sample_stratified_kernel with lindisp = 0, perturb = 1: the depth of lattice sample k < K of ray r
+__device__ __forceinline__ float jitter_depth(const MarchArgs& a, const JitterArgs& j, const MarchRay& m, int64_t r,
+                                              int k, uint64_t seed, uint64_t offset) {
+    const float z = march_depth(m, a.t[k]);
+    const float zl = k > 0 ? march_depth(m, a.t[k - 1]) : 0.f;
+    const float zh = k + 1 < a.K ? march_depth(m, a.t[k + 1]) : 0.f;
+    const float upper = k + 1 < a.K ? 0.5f * (zh + z) : z;
+    const float lower = k > 0 ? 0.5f * (z + zl) : z;
+    const int64_t i = r * a.K + k;
+    const float u = j.u ? j.u[i] : philox_uniform(seed, offset, (uint64_t)i);
+    return lower + (upper - lower) * u;
+}
+
+// march_sample at the jittered depth
+__device__ __forceinline__ bool jitter_sample(const MarchArgs& a, const JitterArgs& j, const MarchRay& m, int64_t r,
+                                              int k, uint64_t seed, uint64_t offset, float& z, float* p) {
+    z = jitter_depth(a, j, m, r, k, seed, offset);
+    p[0] = m.o[0] + m.d[0] * z;
+    p[1] = m.o[1] + m.d[1] * z;
+    p[2] = m.o[2] + m.d[2] * z;
+    return occ_occupied(a.g, a.bits, p);
+}
+
+// march_count_kernel over the whole lattice at the jittered depths
+__global__ void __launch_bounds__(kMarchThreads) jitter_count_kernel(MarchArgs a, JitterArgs j) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
+    if (r >= a.R) return;   // wave-uniform
+    const MarchRay m = march_ray(a, r);
+    const uint64_t seed = j.rng ? j.rng[0] : j.seed, offset = j.rng ? j.rng[1] : j.offset;
+    int n = 0;
+    for (int kb = 0; kb < a.K; kb += 64) {
+        const int k = kb + lane;
+        bool on = false;
+        if (k < a.K) {
+            float z, p[3];
+            on = jitter_sample(a, j, m, r, k, seed, offset, z, p);
+        }
+        n += __popcll(__ballot(on));
+    }
+    if (lane == 0) {
+        a.counts[r] = n;
+        if (a.rays_d) {
+            a.rays_d[3 * r] = m.d[0]; a.rays_d[3 * r + 1] = m.d[1]; a.rays_d[3 * r + 2] = m.d[2];
+        }
+    }
+}
+
+// march_write_kernel over the whole lattice at the jittered depths, one iteration ahead of its stores: dist needs the
+// next sample's jittered depth, which lane 63 finds in lane 0 of the iteration ahead
+template <bool kRays>
+__global__ void __launch_bounds__(kMarchThreads) jitter_write_kernel(MarchArgs a, JitterArgs j) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * kMarchWaves + (threadIdx.x >> 6);
+    if (r >= a.R) return;   // wave-uniform
+    if (a.counts[r] == 0) return;
+    const MarchRay m = march_ray(a, r);
+    const uint64_t seed = j.rng ? j.rng[0] : j.seed, offset = j.rng ? j.rng[1] : j.offset;
+    float sh[16] = {};
+    if constexpr (!kRays) {
+        const float* v = a.rays + r * a.C + 8;
+        sh4_eval(v[0], v[1], v[2], sh);
+    }
+    const uint64_t below = lane == 0 ? 0ull : (~0ull >> (64 - lane));
+    int64_t base = a.off[r];
+    bool on = false;
+    float z = 0.f, p[3] = {0.f, 0.f, 0.f};
+    if (lane < a.K) on = jitter_sample(a, j, m, r, lane, seed, offset, z, p);
+    for (int kb = 0; kb < a.K; kb += 64) {   // every lane of the wave takes part in the moves below
+        const int k = kb + lane;
+        bool on_n = false;
+        float z_n = 0.f, p_n[3] = {0.f, 0.f, 0.f};
+        if (k + 64 < a.K) on_n = jitter_sample(a, j, m, r, k + 64, seed, offset, z_n, p_n);
+        const float z_ahead = __shfl(z_n, 0, 64);   // z of lattice index kb + 64 (0.f past the lattice: not used)
+        float z_up = __shfl_down(z, 1, 64);
+        if (lane == 63) z_up = z_ahead;
+        const uint64_t mask = __ballot(on);
+        const int64_t idx = base + __popcll(mask & below);
+        if (on && idx >= 0 && idx < a.capacity) {
+            a.pts_c[3 * idx] = p[0]; a.pts_c[3 * idx + 1] = p[1]; a.pts_c[3 * idx + 2] = p[2];
+            a.z_c[idx] = z;
+            a.dist_c[idx] = k + 1 < a.K ? z_up - z : 1e10f;
+            if constexpr (kRays) {
+                a.ray_c[idx] = (int32_t)r;
+            } else {
+                float4* dst = reinterpret_cast<float4*>(a.sh_c + 16 * idx);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) dst[q] = make_float4(sh[4 * q], sh[4 * q + 1], sh[4 * q + 2], sh[4 * q + 3]);
+            }
+        }
+        base += __popcll(mask);
+        on = on_n; z = z_n; p[0] = p_n[0]; p[1] = p_n[1]; p[2] = p_n[2];
     }
 }
 
@@ -496,6 +621,75 @@ extern "C" int nerf_rays_slab_march_write(const float* d_rays, int64_t n_rays, i
     return march_write("rays_slab_march_write", d_rays, n_rays, n_cols, d_t, n_samples, k0, k1, bbox_min, bbox_max, res,
                        d_bits, d_counts, d_offsets, n_points, capacity, d_pts_c, d_z_c, d_dist_c, nullptr, true, d_ray_c,
                        stream);
+}
+
+// the jittered lattice: the two walks over the whole lattice with the sampler's uniforms
+static int jitter_uniforms(JitterArgs& j, const char* what, const float* d_u, uint64_t seed, uint64_t offset,
+                           const uint64_t* d_rng) {
+    NERF_REQUIRE(!d_rng || ((uintptr_t)d_rng & 7) == 0, "%s: the device (seed, offset) pair must be 8-B aligned", what);
+    j.u = d_u; j.seed = seed; j.offset = offset; j.rng = d_rng;
+    return NERF_OK;
+}
+
+extern "C" int nerf_jitter_march_count(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                       int64_t n_samples, const float* bbox_min, const float* bbox_max, int res,
+                                       const uint32_t* d_bits, int32_t* d_counts, int32_t* d_offsets, float* d_rays_d,
+                                       void* d_workspace, size_t workspace_bytes, const float* d_u, uint64_t seed,
+                                       uint64_t offset, const uint64_t* d_rng, void* stream) {
+    const char* what = "jitter_march_count";
+    MarchArgs a{};
+    JitterArgs j{};
+    int rc = march_args(a, what, n_rays, n_cols, n_samples, 0, n_samples > 0 ? n_samples : 0, bbox_min, bbox_max, res,
+                        true, d_workspace, workspace_bytes);
+    if (rc) return rc;
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets, "%s: null arg", what);
+    rc = jitter_uniforms(j, what, d_u, seed, offset, d_rng);
+    if (rc) return rc;
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = d_counts; a.off = d_offsets; a.rays_d = d_rays_d;
+    hipLaunchKernelGGL(jitter_count_kernel, dim3(blocks_for(n_rays, kMarchWaves)), dim3(kMarchThreads), 0,
+                       as_stream(stream), a, j);
+    const dim3 scan_grid(blocks_for(n_rays, kCompactBlock));
+    hipLaunchKernelGGL(march_block_counts_kernel, scan_grid, dim3(kCompactThreads), 0, as_stream(stream), a);
+    hipLaunchKernelGGL(march_offsets_kernel, scan_grid, dim3(kCompactThreads), 0, as_stream(stream), a);
+    NERF_CHECK_LAUNCH(what);
+    return NERF_OK;
+}
+
+extern "C" int nerf_jitter_march_write(const float* d_rays, int64_t n_rays, int n_cols, const float* d_t,
+                                       int64_t n_samples, const float* bbox_min, const float* bbox_max, int res,
+                                       const uint32_t* d_bits, const int32_t* d_counts, const int32_t* d_offsets,
+                                       int64_t n_points, int64_t capacity, float* d_pts_c, float* d_z_c,
+                                       float* d_dist_c, float* d_sh_c, int32_t* d_ray_c, const float* d_u,
+                                       uint64_t seed, uint64_t offset, const uint64_t* d_rng, void* stream) {
+    const char* what = "jitter_march_write";
+    MarchArgs a{};
+    JitterArgs j{};
+    int rc = march_args(a, what, n_rays, n_cols, n_samples, 0, n_samples > 0 ? n_samples : 0, bbox_min, bbox_max, res,
+                        false, nullptr, 0);
+    if (rc) return rc;
+    NERF_REQUIRE(n_points >= 0 && n_points <= n_rays * n_samples, "%s: count %lld of %lld lattice samples", what,
+                 (long long)n_points, (long long)(n_rays * n_samples));
+    NERF_REQUIRE(capacity >= n_points, "%s: capacity %lld below the count %lld", what, (long long)capacity,
+                 (long long)n_points);
+    if (n_rays == 0) return NERF_OK;
+    NERF_REQUIRE((d_sh_c != nullptr) != (d_ray_c != nullptr),
+                 "%s: exactly one of sh_c (SH rows) and ray_c (ray indices) must be given", what);
+    if (n_points == 0) return NERF_OK;
+    NERF_REQUIRE(d_rays && d_t && d_bits && d_counts && d_offsets && d_pts_c && d_z_c && d_dist_c, "%s: null arg",
+                 what);
+    NERF_REQUIRE(!d_sh_c || (n_cols == 11 && ((uintptr_t)d_sh_c & 15) == 0),
+                 "%s: SH rows need ray rows of 11 columns and a 16-B aligned sh_c", what);
+    rc = jitter_uniforms(j, what, d_u, seed, offset, d_rng);
+    if (rc) return rc;
+    a.bits = d_bits; a.rays = d_rays; a.t = d_t; a.counts = const_cast<int32_t*>(d_counts);
+    a.off = const_cast<int32_t*>(d_offsets);
+    a.capacity = capacity; a.pts_c = d_pts_c; a.z_c = d_z_c; a.dist_c = d_dist_c; a.sh_c = d_sh_c; a.ray_c = d_ray_c;
+    const dim3 grid(blocks_for(n_rays, kMarchWaves)), block(kMarchThreads);
+    if (d_ray_c) hipLaunchKernelGGL(jitter_write_kernel<true>, grid, block, 0, as_stream(stream), a, j);
+    else hipLaunchKernelGGL(jitter_write_kernel<false>, grid, block, 0, as_stream(stream), a, j);
+    NERF_CHECK_LAUNCH(what);
+    return NERF_OK;
 }
 
 // the kShRecord record of every packed ray row's view direction (ray_sh_records_kernel)

@@ -228,12 +228,22 @@ class OccupancyGrid:
         return hit, span, rows, rays_c
 
     # ---- grid ray marching (csrc/march.hip) ----------------------------------------
-    def _march_count(self, rays, K, k0=None, k1=None, alive=None, dirs=True, sized="host"):
+    @staticmethod
+    def _jitter_args(jitter):
+        """The uniforms of a jittered walk as the nerf_jitter_ entries take them: jitter = (u float32
+        [R, K] or None, seed, offset, d_rng or None), the sampler's four."""
+        u, seed, off, rng = jitter
+        return _lib.ptr(u, "u", allow_none=True), int(seed), int(off), rng
+
+    def _march_count(self, rays, K, k0=None, k1=None, alive=None, dirs=True, sized="host", jitter=None):
         """nerf_march_count over packed rows -> (rays, t, counts [R], offsets [R + 1], rays_d [R, 3], n). With a
         lattice range [k0, k1) (and alive, uint8 [R], or None for every ray): nerf_slab_march_count over that range
         of the rays alive. dirs=False: rays_d is not written (None). sized="device" (DESIGN.md §23):
-        n is the device element offsets[R:R + 1], int32 [1], and the host reads nothing."""
+        n is the device element offsets[R:R + 1], int32 [1], and the host reads nothing. jitter (the
+        whole lattice, host-sized): nerf_jitter_march_count with these uniforms (_jitter_args)."""
         from .render import _linspace
+        if jitter is not None and (k0 is not None or sized == "device"):
+            raise ValueError("OccupancyGrid.march: a jittered walk has no slab and no device-sized entries")
         rays = _packed_rows(rays, "march")
         K = check_march_samples(K, "OccupancyGrid.march")
         R, C, dev = rays.shape[0], rays.shape[1], rays.device
@@ -246,20 +256,22 @@ class OccupancyGrid:
         n = 0
         if R > 0:
             ws = torch.empty(int(_lib.load().nerf_march_workspace_bytes(R)) // 4, **i32)
-            name, slab = "nerf_march_count", ()
+            name, slab, uniforms = "nerf_march_count", (), ()
             if k0 is not None:
                 name, slab = "nerf_slab_march_count", (int(k0), int(k1), _lib.ptr(alive, "alive", torch.uint8, True))
+            if jitter is not None:
+                name, uniforms = "nerf_jitter_march_count", self._jitter_args(jitter)
             _lib.call(name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab, self._bmin, self._bmax,
                       self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
                       _lib.ptr(offsets, "offsets", torch.int32), _lib.ptr(rays_d, "rays_d", allow_none=True),
-                      _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, _lib.stream())
+                      _lib.ptr(ws, "workspace", torch.int32), ws.numel() * 4, *uniforms, _lib.stream())
             if sized != "device":
                 n = int(offsets[R].item())     # one 4-byte host read sizes the list
         if sized == "device":
             n = offsets[R:R + 1]
         return rays, t, counts, offsets, rays_d, n
 
-    def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None, index=False):
+    def _march_write(self, rays, t, K, counts, offsets, n, sh, k0=None, k1=None, index=False, jitter=None):
         """nerf_march_write of the list _march_count sized; with the same [k0, k1): nerf_slab_march_write.
         index: the nerf_rays_ write; the fourth result is then ray_c int32 [n], the row of each
         entry's ray in `rays`, and no SH row is formed. n a device element (_march_count sized="device", DESIGN.md
@@ -277,7 +289,13 @@ class OccupancyGrid:
         else:
             last = torch.empty(n, 16, **f) if sh else None
             last_ptr = _lib.ptr(last, "sh_c", allow_none=True)
-        if n > 0:
+        if n > 0 and jitter is not None:
+            _lib.call("nerf_jitter_march_write", _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, self._bmin,
+                      self._bmax, self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),
+                      _lib.ptr(offsets, "offsets", torch.int32), n, n, _lib.ptr(pts_c, "pts_c"), _lib.ptr(z_c, "z_c"),
+                      _lib.ptr(dist_c, "dist_c"), None if index else last_ptr, last_ptr if index else None,
+                      *self._jitter_args(jitter), _lib.stream())
+        elif n > 0:
             name, slab = ("nerf_march_write", ()) if k0 is None else ("nerf_slab_march_write", (int(k0), int(k1)))
             _lib.call(name.replace("nerf_", "nerf_rays_") if index else name, _lib.ptr(rays, "rays"), R, C, _lib.ptr(t, "t"), K, *slab,
                       self._bmin, self._bmax, self.resolution, self._bits(), _lib.ptr(counts, "counts", torch.int32),

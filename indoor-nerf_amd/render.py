@@ -441,7 +441,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                 pytest=False, predict_normals=False, occupancy=None, early_stop=None, early_stop_slab=32,
                 march=None, march_samples=512, march_points=1 << 21, mlp_precision=None,
                 table_precision=None, march_stop=None, march_stop_slab=128, feature_precision=None, march_sh=None,
-                march_sizes=None, march_grad=False):
+                march_sizes=None, march_grad=False, march_jitter=False):
     """run_nerf.py:414-549. occupancy (an occupancy.OccupancyGrid; forward-only rendering):
     the field runs only at the samples inside the box and in an occupied cell, every other sample gets an
     all-zero raw row (weight 0). None (the default) is the dense path.
@@ -503,13 +503,22 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     is attached to the graph. Under torch.no_grad() the call is the march without it: the same launches, the same
     bits. Does not combine with march_stop= (the slabs' carried state has no backward); march_sh="rays",
     mlp_precision="bf16", table_precision="fp16", feature_precision="bf16" and march_sizes="device" stay forward-only.
-    False (the default) leaves every call as it is: march= under gradients is refused."""
+    False (the default) leaves every call as it is: march= under gradients is refused.
+    march_jitter (a bool; with march=): True lets the march take perturb > 0: lattice sample k of a ray
+    then lies at the depth the dense coarse sampler gives it with perturb (uniform in its stratum, bit for bit; with
+    pytest the reference's np.random.seed(0) uniforms, else an in-kernel Philox draw that render.manual_seed makes
+    repeatable, one seed per chunk), and the packed dists are those of the jittered depths. With perturb == 0 the call
+    is the plain march: the same launches, the same bits, so one dict serves training and evaluation. Composes with
+    march_grad under gradients, and with march_sh, mlp_precision, table_precision, feature_precision and march_points
+    under torch.no_grad(). Does not combine with march_stop=, march_sizes="device" or render's ray_bounds=. False
+    (the default) leaves every call as it is: march= with perturb > 0 is refused."""
     # march_sizes is passed only when given: tests/test_field_request.py pins this call's eight positional arguments
     # and empty keywords for a call without it (the same in render())
     opts = sparse_field.field_options("render_rays", march, march_sh, march_stop, march_stop_slab, mlp_precision,
                                       table_precision, feature_precision,
                                       **({} if march_sizes is None else dict(march_sizes=march_sizes)))
     march_grad = sparse_field.check_march_grad(march_grad, march, opts.stop, "render_rays")
+    march_jitter = sparse_field.check_march_jitter(march_jitter, march, opts.stop, march_sizes, "render_rays")
     nets = [network_fn] + ([] if network_fine is None else [network_fine])
     if opts.half:
         sparse_field.check_table_nets(nets, embed_fn)
@@ -520,7 +529,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
                                   embed_fn=embed_fn, retraw=retraw, lindisp=lindisp, perturb=perturb,
                                   network_fine=network_fine, white_bkgd=white_bkgd, raw_noise_std=raw_noise_std,
                                   predict_normals=predict_normals, occupancy=occupancy, early_stop=early_stop,
-                                  device_sizes=sparse_field.device_sized(march_sizes), march_grad=march_grad)
+                                  device_sizes=sparse_field.device_sized(march_sizes), march_grad=march_grad,
+                                  march_jitter=march_jitter, pytest=pytest)
     early = None
     if early_stop is not None:
         from .early_stop import check_params
@@ -636,9 +646,9 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
 
 
 def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, perturb, raw_noise_std, predict_normals,
-                 occupancy, early_stop, march_grad=False):
+                 occupancy, early_stop, march_grad=False, march_jitter=False):
     """render_rays' refusals with march= after field_options', all before any launch -> K. march_grad: the call may
-    run under gradients."""
+    run under gradients. march_jitter: the call may carry perturb > 0."""
     from .occupancy import OccupancyGrid, _check_modules, check_march_samples
     from .sparse_field import check_forward_only, check_march_points
     if not isinstance(grid, OccupancyGrid):
@@ -649,7 +659,7 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
         raise ValueError("render_rays: march does not combine with occupancy= (the march already masks by its grid) "
                          "or early_stop= (rays are not stopped inside a march)")
     check_forward_only("march", "render_rays", raw_noise_std, grad=march_grad)
-    if perturb > 0.:
+    if perturb > 0. and not march_jitter:
         raise ValueError("render_rays: march needs perturb == 0 (the lattice is the unperturbed coarse sampling)")
     if lindisp:
         raise ValueError("render_rays: march needs lindisp=False (the lattice is linear in depth)")
@@ -662,7 +672,8 @@ def _check_march(grid, march_samples, march_points, fn, embed_fn, lindisp, pertu
 
 def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samples, march_points, opts, embed_fn=None,
                        retraw=False, lindisp=False, perturb=0., network_fine=None, white_bkgd=False, raw_noise_std=0.,
-                       predict_normals=False, occupancy=None, early_stop=None, device_sizes=False, march_grad=False):
+                       predict_normals=False, occupancy=None, early_stop=None, device_sizes=False, march_grad=False,
+                       march_jitter=False, pytest=False):
     """render_rays with march=: count and write the packed list (csrc/march.hip), the field on
     the list (sparse_field.run_network_packed), the packed compositing. opts: the call's FieldOptions. With
     opts.stop (march_stop) the same in slabs (_march_slabs). opts.by_ray (march_sh="rays", DESIGN.md
@@ -672,10 +683,12 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
     segment into the list, and every offset is at most the true length, which is at most the capacity) and the field
     runs whenever the capacity is not 0. march_grad under gradients: the field call's list allows
     gradients (field.PackedFieldFn), the compositing is MarchCompositeFn, and both run for an empty list too, so that
-    the maps stay attached to the graph."""
+    the maps stay attached to the graph. march_jitter with perturb > 0: the count and the write are the
+    nerf_jitter_ entries with the dense coarse pass's uniforms (pytest: _pytest_uniforms((R, K)); else one _rng() draw
+    per chunk); everything after the write takes the jittered list unchanged."""
     run_fn = network_fn if network_fine is None else network_fine
     K = _check_march(grid, march_samples, march_points, run_fn, embed_fn, lindisp, perturb, raw_noise_std,
-                     predict_normals, occupancy, early_stop, march_grad)
+                     predict_normals, occupancy, early_stop, march_grad, march_jitter)
     train = march_grad and torch.is_grad_enabled()   # march_sh="rays" and march_sizes="device" have refused gradients
     if not torch.is_tensor(ray_batch) or ray_batch.dim() != 2 or ray_batch.shape[1] != 11:
         raise ValueError("render_rays: march needs ray rows with view directions ([R, 11]: use_viewdirs=True)")
@@ -700,9 +713,14 @@ def _render_rays_march(ray_batch, network_fn, network_query_fn, grid, march_samp
         if DEBUG:
             check_numerics(ret)
         return ret
-    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K, sized="device" if device_sizes else "host")
+    jitter = None
+    if march_jitter and perturb > 0.:   # the dense coarse pass's uniforms: the same draws in the same order
+        u = _pytest_uniforms((ray_batch.shape[0], K), ray_batch.device) if pytest else None
+        jitter = (u,) + ((0, 0, None) if u is not None else _rng())
+    rays, t, counts, offsets, rays_d, n = grid._march_count(ray_batch, K, sized="device" if device_sizes else "host",
+                                                            jitter=jitter)
     R, dev = rays.shape[0], rays.device
-    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, index=by_ray)
+    pts_c, z_c, dist_c, sh_c = grid._march_write(rays, t, K, counts, offsets, n, True, index=by_ray, jitter=jitter)
     f = dict(device=dev, dtype=torch.float32)
     if device_sizes:
         grid._last = ([n], R * K)        # the count as device elements, one per list: last_counts() reads them when asked
@@ -970,7 +988,8 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
     spans its own [near', far']. mlp_precision and table_precision go to
     render_rays as well, and so do march_stop and march_stop_slab and feature_precision (DESIGN.md
     §20), march_sh and march_sizes (the one count read per frame of ray_bounds stays),
-    and march_grad (the march under gradients; ray_bounds stays forward-only).
+    and march_grad (the march under gradients; ray_bounds stays forward-only) and march_jitter
+    (perturb > 0 jitters the march's lattice; refused with ray_bounds).
     retraw is refused with march: the packed entries of several chunks do not
     concatenate."""
     # render_rays' value checks, also when no chunk reaches it (ray_bounds with every ray missed)
@@ -981,6 +1000,10 @@ def render(H, W, K, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far
                                       **({} if kwargs.get("march_sizes") is None
                                          else dict(march_sizes=kwargs["march_sizes"])))
     sparse_field.check_march_grad(kwargs.get("march_grad", False), kwargs.get("march"), opts.stop, "render")
+    if sparse_field.check_march_jitter(kwargs.get("march_jitter", False), kwargs.get("march"), opts.stop,
+                                       kwargs.get("march_sizes"), "render") and ray_bounds is not None:
+        raise ValueError("render: march_jitter=True does not combine with ray_bounds= (a bounded ray's lattice has no "
+                         "jittered entries)")
     if kwargs.get("march") is not None and kwargs.get("retraw"):
         raise ValueError("render: retraw is not available with march (the packed entries of several chunks do not "
                          "concatenate; call render_rays on one chunk)")

@@ -336,6 +336,26 @@ def check_march_grad(value, march, stop, prefix):
     return True
 
 
+def check_march_jitter(value, march, stop, march_sizes, prefix):
+    """march_jitter of `prefix` (render_rays, render) -> whether perturb > 0 jitters the march's lattice (DESIGN.md
+    §25); its refusals, one fixed sentence each: a value that is not a bool, True without march=, True with march_stop=
+    (stop: check_march_stop's answer) or with march_sizes="device": the slab walk and the device-sized path have no
+    jittered entries. It follows field_options and check_march_grad."""
+    if not isinstance(value, bool):
+        raise ValueError(f"{prefix}: march_jitter must be a bool, got {value!r}")
+    if not value:
+        return False
+    if march is None:
+        raise ValueError(f"{prefix}: march_jitter=True needs march= (the jitter is that of a grid march's lattice)")
+    if stop is not None:
+        raise ValueError(f"{prefix}: march_jitter=True does not combine with march_stop= (the slab walk has no jittered "
+                         "entries)")
+    if device_sized(march_sizes):
+        raise ValueError(f"{prefix}: march_jitter=True does not combine with march_sizes='device' (the device-sized "
+                         "path has no jittered entries)")
+    return True
+
+
 def check_forward_only(what, prefix, raw_noise_std=0., grad=False):
     """The refusals every forward-only keyword `what` of `prefix` (render_rays, render) shares: no gradients (grad:
     the call carries march_grad=True), no raw noise."""
